@@ -11,9 +11,14 @@ Multi-GPU: launched by torch.distributed.run, one process per GPU; envs are
 sharded (4096 per rank, weak scaling) and PPO all-reduces one flat gradient
 bucket per optimizer step over RCCL.
 
-Extra fields: env-only and rollout throughput, the live-timed fused env-step
-kernel against the HBM roofline (algorithmic bytes), and the CPU
-oracle baseline (rank 0, N=1 only).
+A plain run sets up, warms up, times the K iterations and prints the result line.
+--dump-outputs DIR writes what the last timed iteration left (the policy, the rollout
+storage, the env's buffers) as DIR/<name>.npy; the run is seeded, so two builds can be
+compared array for array.
+
+--full adds, outside the timed region: env-only and rollout throughput, the live-timed
+fused env-step kernel against the HBM roofline (algorithmic bytes), the
+other BASELINE configs and the CPU oracle baseline (rank 0, N=1 only).
 """
 import argparse
 import contextlib
@@ -37,6 +42,11 @@ def parse():
     p.add_argument("--steps", type=int, default=10, help="timed PPO iterations")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--num_envs", type=int, default=NUM_ENVS)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed iteration's outputs as DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: env-only, rollout, roofline, the other "
+                        "BASELINE configs, the CPU baseline (the options below shape them)")
     p.add_argument("--env_steps", type=int, default=200, help="timed control steps of the env-only leg")
     p.add_argument("--cpu_seconds", type=float, default=12.0, help="budget of the CPU oracle baseline")
     p.add_argument("--no_cpu_baseline", action="store_true")
@@ -405,26 +415,11 @@ def env_kernel_rate(task, n, dev, steps, get_args, task_registry):
     return out
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(args))
+def env_and_rollout_legs(env, runner, args, dev, rank):
+    """--full, before the PPO iterations: the env-only and the rollout leg on the benchmark's own
+    env and policy.  Returns the env-step kernel's ms per launch, its capacity drops, and the
+    env-only and rollout env-steps/s."""
     import torch
-    import isaacgym  # noqa: F401
-    from legged_gym.envs import task_registry  # noqa: F401  (before legged_gym.utils: the registry's import order)
-    world, rank, dev = setup_dist(args)
-    if args.gpus != world:
-        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
-    from legged_gym.utils import get_args
-    from legged_gym.utils.helpers import class_to_dict
-    from rsl_rl.runners import OnPolicyRunner
-
-    gargs = get_args(["--task", "go2", "--num_envs", str(args.num_envs), "--headless", "--sim_device", dev,
-                      "--rl_device", dev])
-    with contextlib.redirect_stdout(sys.stderr):  # stdout carries only the JSON line
-        env, env_cfg = task_registry.make_env(name="go2", args=gargs)
-        _, train_cfg = task_registry.get_cfgs("go2")
-        runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir=None, device=dev)
     T = runner.num_steps_per_env
     N = env.num_envs
 
@@ -469,6 +464,67 @@ def main():
             obs, _, _, _, _ = env.step(runner.alg.actor_critic.act(obs))
         torch.cuda.synchronize(dev)
     rollout = N * 2 * T / (time.time() - t0)
+    return kernel_ms, go2_drops, env_only, rollout
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # .npy headers on top stay under 64 MB
+
+
+def dump_outputs(path, runner, env):
+    """What a caller of the timed runner.learn() holds after its last iteration, as
+    <path>/<name>.npy (float32): the updated policy's parameters, the rollout storage of that
+    iteration (observations, actions, policy outputs, rewards, values, returns, advantages) and
+    the env's buffers after its last control step.  At most DUMP_BUDGET_BYTES in all: where the
+    arrays exceed it, each one above its even share is cut to a fixed, seeded sample of its
+    elements."""
+    import numpy as np
+    import torch
+    st = runner.alg.storage
+    arrays = {f"policy.{k}": v for k, v in runner.alg.actor_critic.named_parameters()}
+    for k in ("observations", "privileged_observations", "actions", "actions_log_prob", "mu", "sigma", "values",
+              "rewards", "dones", "returns", "advantages"):
+        if getattr(st, k, None) is not None:
+            arrays[f"rollout.{k}"] = getattr(st, k)
+    for k in ("obs_buf", "privileged_obs_buf", "rew_buf", "reset_buf", "episode_length_buf", "root_states",
+              "dof_pos", "dof_vel"):
+        if getattr(env, k, None) is not None:
+            arrays[f"env.{k}"] = getattr(env, k)
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy() for k, v in arrays.items()}
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(args))
+    import torch
+    import isaacgym  # noqa: F401
+    from legged_gym.envs import task_registry  # noqa: F401  (before legged_gym.utils: the registry's import order)
+    world, rank, dev = setup_dist(args)
+    if args.gpus != world:
+        raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    from legged_gym.utils import get_args
+    from legged_gym.utils.helpers import class_to_dict
+    from rsl_rl.runners import OnPolicyRunner
+
+    gargs = get_args(["--task", "go2", "--num_envs", str(args.num_envs), "--headless", "--sim_device", dev,
+                      "--rl_device", dev])
+    with contextlib.redirect_stdout(sys.stderr):  # stdout carries only the JSON line
+        env, env_cfg = task_registry.make_env(name="go2", args=gargs)
+        _, train_cfg = task_registry.get_cfgs("go2")
+        runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir=None, device=dev)
+    T = runner.num_steps_per_env
+    N = env.num_envs
+    if args.full:
+        kernel_ms, go2_drops, env_only, rollout = env_and_rollout_legs(env, runner, args, dev, rank)
 
     # ---- full PPO iterations (the metric)
     runner.learn(num_learning_iterations=args.warmup, init_at_random_ep_len=True)
@@ -486,9 +542,8 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
-    bytes_per_launch = GO2_BYTES_PER_ENV_STEP * N
-    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
-    pmc = load_pmc() or {}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, env)
     line = {
         "metric": "env-steps/sec + PPO-iter wall-time, Go2 4096 envs/GPU at 1/2/4/8 MI355X",
         "value": round(value, 1),
@@ -506,6 +561,22 @@ def main():
                    "num_envs_per_gpu": N, "decimation": env_cfg.control.decimation,
                    "parallelism": f"dp{world}"},
         "ppo_iter_ms": round(ms_per_iter, 3),
+    }
+    if args.full:
+        line.update(full_fields(args, env, dev, world, N, kernel_ms, go2_drops, env_only, rollout))
+    print(json.dumps(line), flush=True)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def full_fields(args, env, dev, world, N, kernel_ms, go2_drops, env_only, rollout):
+    """--full: the result line's fields beside the headline figure."""
+    from legged_gym.envs import task_registry
+    from legged_gym.utils import get_args
+    bytes_per_launch = GO2_BYTES_PER_ENV_STEP * N
+    achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9
+    pmc = load_pmc() or {}
+    line = {
         "env_only_env_steps_per_s": round(env_only, 1),
         "rollout_env_steps_per_s": round(rollout, 1),
         "env_step_kernel_ms": round(kernel_ms, 4),
@@ -538,9 +609,7 @@ def main():
         line["h1_2_8192_ppo_iter_ms"] = line["other_configs_ppo_iter"]["h1_2_8192"]["ppo_iter_ms"]
     if world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(env, args.cpu_seconds)
-    print(json.dumps(line), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    return line
 
 
 if __name__ == "__main__":

@@ -15,10 +15,16 @@ storages:
 The fixture's outputs are then re-derived from those weights with torch's nn.LSTM by
 tests/test_rsl_rl.py (CPU) and through the HIP LSTM by tests/test_gpu_recurrent.py.
 
-Test infrastructure (tests/test_golden_lstm_archive.py); reads /root/reference, so it runs in
-the build container only.
+The archives' storages are recorded as their lengths and SHA-256 digests in
+tests/golden/lstm_archive_storages.json, so the check needs no archive: a fixture array equals a
+storage when its bytes have the storage's length and digest.  With a reference root the storages
+are read from the archives themselves (and, with --record, written to that file).
 
-usage: python oracle/check_lstm_fixtures.py [reference_root]"""
+Test infrastructure (tests/test_golden_lstm_archive.py).
+
+usage: python oracle/check_lstm_fixtures.py [--record] [reference_root]"""
+import hashlib
+import json
 import os
 import sys
 import zipfile
@@ -27,25 +33,40 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "..", "tests", "golden")
+RECORD = os.path.join(GOLDEN, "lstm_archive_storages.json")
 ROBOTS = ("g1", "h1", "h1_2")
 
 
+def _digest(raw):
+    return {"nbytes": len(raw), "sha256": hashlib.sha256(raw).hexdigest()}
+
+
 def storages(archive):
-    """{index: raw bytes} of the archive's tensor storages (zip entries '<top>/data/<i>')."""
+    """{index: length and digest} of the archive's tensor storages (zip entries '<top>/data/<i>')."""
     out = {}
     with zipfile.ZipFile(archive) as z:
         for name in z.namelist():
             head, _, leaf = name.rpartition("/")
             if head.endswith("/data") and leaf.isdigit():
-                out[int(leaf)] = z.read(name)
+                out[int(leaf)] = _digest(z.read(name))
     return out
 
 
+def recorded(robot):
+    """The same, from the record of the archives' storages under tests/golden."""
+    with open(RECORD) as f:
+        return {int(i): d for i, d in json.load(f)[robot].items()}
+
+
 def check(reference_root, robot):
-    """Returns a list of mismatch descriptions (empty: the fixture is the archive's weights)."""
+    """Returns a list of mismatch descriptions (empty: the fixture is the archive's weights).
+    reference_root None: against the recorded storages."""
     fx = np.load(os.path.join(GOLDEN, f"lstm_policy_{robot}.npz"))  # arrays only (allow_pickle=False)
     weights = [k for k in fx.files if k.startswith("w.")]
-    st = storages(os.path.join(reference_root, "deploy", "pre_train", robot, "motion.pt"))
+    if reference_root is None:
+        st = recorded(robot)
+    else:
+        st = storages(os.path.join(reference_root, "deploy", "pre_train", robot, "motion.pt"))
     bad = []
     if sorted(st) != list(range(len(weights))):
         bad.append(f"{robot}: archive storages {sorted(st)} vs {len(weights)} fixture weights")
@@ -53,10 +74,10 @@ def check(reference_root, robot):
     for i, k in enumerate(weights):
         a = np.ascontiguousarray(fx[k], dtype="<f4").tobytes()
         if k in state:
-            if st.get(i) != bytes(len(a)):
+            if st.get(i) != _digest(bytes(len(a))):
                 bad.append(f"{robot}: archive storage {i} ({k}) is not the zero reset state")
-        elif st.get(i) != a:
-            bad.append(f"{robot}: {k} != archive storage {i} ({len(a)} vs {len(st.get(i, b''))} bytes)")
+        elif st.get(i) != _digest(a):
+            bad.append(f"{robot}: {k} != archive storage {i} ({len(a)} vs {(st.get(i) or {}).get('nbytes', 0)} bytes)")
     import torch  # the memory's state after the fixture's 5-step post-reset run
     lstm = torch.nn.LSTM(fx["w.memory.weight_ih_l0"].shape[1], fx["w.memory.weight_hh_l0"].shape[1], 1)
     lstm.load_state_dict({k[len("w.memory."):]: torch.from_numpy(fx[k]) for k in weights if k.startswith("w.memory.")})
@@ -68,7 +89,15 @@ def check(reference_root, robot):
     return bad
 
 
-def main(reference_root):
+def main(argv):
+    record = "--record" in argv
+    roots = [a for a in argv if a != "--record"]
+    reference_root = roots[0] if roots else None
+    if record:
+        with open(RECORD, "w") as f:
+            json.dump({r: storages(os.path.join(reference_root, "deploy", "pre_train", r, "motion.pt")) for r in ROBOTS},
+                      f, indent=1)
+            f.write("\n")
     bad = [m for r in ROBOTS for m in check(reference_root, r)]
     for m in bad:
         print(m)
@@ -79,4 +108,4 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else "/root/reference"))
+    sys.exit(main(sys.argv[1:]))

@@ -26,7 +26,7 @@ def test_bench_two_ranks_one_json_line():
     env.pop("WORLD_SIZE", None)
     steps = 2
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1",
-           "--no_other_configs", "--no_cpu_baseline", "--env_steps", "20"]
+           "--full", "--no_other_configs", "--no_cpu_baseline", "--env_steps", "20"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, f"bench.py --gpus 2 failed ({r.returncode}):\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
