@@ -15,13 +15,17 @@ from leggedsim import native  # noqa: E402
 NAMES = {1: "fk", 2: "inertia", 3: "bias_rnea", 4: "composite", 5: "mass_matrix+rhs", 6: "cholesky",
          7: "qdd+qf", 8: "limits+contact_detect", 9: "contact_rows_J", 10: "Y=L^-1J^T", 11: "A=YtY", 12: "pgs",
          13: "z+backsub+cforce", 14: "integrate", 15: "body_states", 16: "post_physics", 17: "store"}
+# sub-stamps: their cycles belong to the phase named first (the table adds them in)
+SUB = {8: {31: "ground candidates"},
+       16: {24: "base state/commands/term.", 25: "reward terms", 26: "reward total", 27: "reset",
+            28: "push + obs build", 16: "noise + obs store"}}
 
 
 def main(task="go2", n=4096):
     args = get_args(["--task", task, "--num_envs", str(n), "--headless"])
     env, _ = task_registry.make_env(name=task, args=args)
     lib = native.load()
-    buf = torch.zeros(n, 24, dtype=torch.int64, device="cuda")
+    buf = torch.zeros(n, 32, dtype=torch.int64, device="cuda")
     lib.lgs_debug_set_phase_buffer.argtypes = [C.c_void_p]
     native.check(lib, lib.lgs_debug_set_phase_buffer(buf.data_ptr()), "set_phase_buffer")
     env.reset()
@@ -34,10 +38,15 @@ def main(task="go2", n=4096):
     rows = rows[rows[:, 1:18].sum(1) > 0]
     b = rows.mean(0).cpu().numpy()
     dec = env.cfg.control.decimation
+    own = b.copy()
+    for i, sub in SUB.items():
+        b[i] = sum(own[k] for k in set(sub) | {i})
     tot = b[1:18].sum()
     print(f"{task} n={n}: cycles per control step (lane-0 wave view, mean over {rows.shape[0]} waves), decimation {dec}: total {tot:.0f}")
     for i in range(1, 18):
         print(f"  {NAMES[i]:24s} {b[i]:10.0f}  {100 * b[i] / tot:5.1f}%")
+        for k, name in SUB.get(i, {}).items():
+            print(f"      {name:28s} {own[k]:8.0f}")
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@ from leggedsim import native  # noqa: E402
 def main(task="go2", n=4096, scale=0.5):
     env, _ = task_registry.make_env(name=task, args=get_args(["--task", task, "--num_envs", str(n), "--headless"]))
     lib = native.load()
-    buf = torch.zeros(n, 24, dtype=torch.int64, device="cuda")
+    buf = torch.zeros(n, 32, dtype=torch.int64, device="cuda")
     lib.lgs_debug_set_phase_buffer.argtypes = [C.c_void_p]
     native.check(lib, lib.lgs_debug_set_phase_buffer(buf.data_ptr()), "set_phase_buffer")
     env.reset()

@@ -32,7 +32,10 @@
 
 // Diagnostic build only (-DLGS_PHASE_STAMPS): lane 0 accumulates s_memtime
 // deltas per phase into a global [N][LGS_NPHASE] buffer.  Never in the real build.
-#define LGS_NPHASE 24
+// 1..17: the phases; 18..23: the wave timeline; 24..28: post-physics from its start to the
+// end of the base-frame block, the reward terms, the reward total, reset, push + obs build
+// (its noise + store part stays in 16); 31: step 8's ground-candidate loop (the rest in 8)
+#define LGS_NPHASE 32
 #ifdef LGS_PHASE_STAMPS
 __device__ unsigned long long* g_phase_buf;
 #define STAMP(i)                                                                                 \
@@ -400,6 +403,8 @@ struct Smem {
     static constexpr int n = 6 + D;
     static constexpr int NP = (n % 2 == 0) ? n + 1 : n;     // odd row stride: conflict-free columns
     static constexpr int AS = (ROWS % 2 == 0) ? ROWS + 1 : ROWS;
+    // reward staging row: the longest element list (DOFs, penalised bodies), odd stride
+    static constexpr int EL = (D > LGS_MAX_CONTACT_BODIES ? D : LGS_MAX_CONTACT_BODIES) | 1;
     float root[16];
     float q[D], qd[D], tau[D], act[D];
     float R[B][9], p[B][3], aw[B][3], cw[B][3];
@@ -422,8 +427,10 @@ struct Smem {
         } fk;
         struct {  // post-physics scratch
             float obs_tmp[LGS_MAX_OBS];
-            float terms[LGS_MAX_REWARDS + 1];
             float misc[32];
+            // reward staging: row k holds the per-DOF / per-foot elements of active term k,
+            // which lane k then adds in index order (EL: the longest such list)
+            float el[LGS_MAX_REWARDS][EL];
         } post;
         struct {  // contact selection (step 8, before any constraint row is written)
             int pwin[B];              // per body: its first touching candidate so far (primary)
@@ -445,6 +452,17 @@ struct Smem {
     float c_sep[ROWS / 3];
     float cf[B][3];
     int flags[8];
+    // post-physics inputs of this env (outside the union: they live through the substeps),
+    // fetched from the env buffers with the state so that their latency is the state load's;
+    // ep is kept current (the increment, a reset's 0) for the push test
+    struct {
+        long long ep;
+        float cmd[4];
+        float last_act[D > 0 ? D : 1], last_qd[D > 0 ? D : 1];
+        float air[LGS_MAX_FEET];
+        int lastc[LGS_MAX_FEET];
+        float sums[LGS_MAX_REWARDS + 1];
+    } pre;
 #ifdef LGS_PHASE_STAMPS
     unsigned long long stamps[LGS_NPHASE];
     unsigned long long tlast;
@@ -491,7 +509,7 @@ __device__ __forceinline__ void load_model(ModelCache<D, B>& c, const DevModel& 
 // -------------------------------------------------------------- substep --
 // One physics substep of this block's env.  Preconditions: s.root/q/qd/tau hold
 // the state and the torques, s.mc the model.  Postcondition: state integrated,
-// s.cf = contact forces of this substep.  All 64 lanes must call it.
+// s.cf = contact forces of this substep if want_cf (else untouched).  All 64 lanes must call it.
 //
 // Register-resident linear algebra (lane i < n owns row i of M / L):
 //   mass matrix row assembled in-lane from the composites; right-looking
@@ -553,7 +571,7 @@ __device__ __forceinline__ void uniform_solve(const float* b, const float (*L)[L
 
 template <int D, int B, int ROWS, int CH, int EPW, bool PAD = false>
 __device__ void substep(Smem<D, B, ROWS>* sm, const ModelCache<D, B>& mc, const DevModel& md, const DevSim& sp,
-                        float added_mass, float shape_mu) {
+                        float added_mass, float shape_mu, bool want_cf) {
     constexpr int n = 6 + D;
     Smem<D, B, ROWS>& s = sm[hh<EPW>()];
     // Opaque lane id: lane-derived addresses are recomputed each substep (a few VALU
@@ -1027,6 +1045,7 @@ __device__ void substep(Smem<D, B, ROWS>* sm, const ModelCache<D, B>& mc, const 
         // others are staged in candidate order.
         int np = 0, nsec = 0;
         const int nch = (md.P + WAVE / EPW - 1) / (WAVE / EPW);
+        STAMP(8);
         for (int ch = 0; ch < nch; ++ch) {
             if (!(chunk_bodies<EPW>(mc, ch) & touch)) continue;  // (wave-uniform: touch above)
             const int k = ch * (WAVE / EPW) + lane;
@@ -1075,6 +1094,7 @@ __device__ void substep(Smem<D, B, ROWS>* sm, const ModelCache<D, B>& mc, const 
             np += __popcll(pm);
             nsec += __popcll(sm_);
         }
+        STAMP(31);
         const int npg = np < maxc ? np : maxc;
         int nsc = nsf < sp.max_self ? nsf : sp.max_self;
         if (nsc > maxc - npg) nsc = maxc - npg;
@@ -1532,8 +1552,8 @@ __device__ void substep(Smem<D, B, ROWS>* sm, const ModelCache<D, B>& mc, const 
         const float lim = mc.vl[D - 1 - lane];
         if (lim > 0.f) qn = fminf(fmaxf(qn, -lim), lim);
     }
-    // contact forces of this substep
-    {
+    // contact forces of this substep (want_cf: a control step reads only its last substep's)
+    if (want_cf) {
         float F[3] = {0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < CM; ++c)
@@ -1680,6 +1700,39 @@ __device__ __forceinline__ void store_state(Smem<D, B, ROWS>& s, const DevState&
     for (int i = lane; i < 3 * Br; i += WAVE / EPW) st.cforce[(size_t)3 * Br * e + i] = (&s.cf[0][0])[i];
 }
 
+// The env's post-physics inputs into s.pre.  Every load is unconditional (a lane beyond a
+// list reads its first entry), so they issue back to back with the state's and the wave
+// waits for one round trip, not one per list; the physics then covers nothing less.
+// The split parts read here what the physics half and a task's Python callback left.
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_post_inputs(Smem<D, B, ROWS>& s, const lgs_task_params& T,
+                                                 const lgs_env_buffers& E, int N, int e, bool post) {
+    const int lane = hl<EPW>();
+    const int A = T.num_actions, Ad = PAD ? A : D, nf = T.num_feet;
+    if (!post) {  // the physics half alone reads the last DOF velocities (a velocity-mode PD)
+        if (lane < Ad) s.pre.last_qd[lane] = E.last_dof_vel[Ad * e + lane];
+        return;
+    }
+    const int nsum = T.num_rewards + (T.has_termination_reward ? 1 : 0);
+    const float la = E.last_actions[A * e + (lane < A ? lane : 0)];
+    const float lq = E.last_dof_vel[Ad * e + (lane < Ad ? lane : 0)];
+    const float cm = E.commands[4 * e + (lane & 3)];
+    const float su = E.episode_sums[(size_t)(lane < nsum ? lane : 0) * N + e];
+    const long long ep = E.episode_length[e];
+    float air = 0.f;
+    int lc = 0;
+    if (nf > 0) {  // (a task without feet binds no such buffers)
+        air = E.feet_air_time[nf * e + (lane < nf ? lane : 0)];
+        lc = E.last_contacts[nf * e + (lane < nf ? lane : 0)];
+    }
+    if (lane < A) s.pre.last_act[lane] = la;
+    if (lane < Ad) s.pre.last_qd[lane] = lq;
+    if (lane < 4) s.pre.cmd[lane] = cm;
+    if (lane < nsum) s.pre.sums[lane] = su;
+    if (lane < nf) { s.pre.air[lane] = air; s.pre.lastc[lane] = lc; }
+    if (lane == 0) s.pre.ep = ep;
+}
+
 // ---------------------------------------------------------- kernels --------
 template <int D, int B, int ROWS, int CH, bool PAD = false>
 __global__ __launch_bounds__(WAVE) void k_simulate(DevModel md, DevSim sp, DevState st, int N) {
@@ -1693,7 +1746,7 @@ __global__ __launch_bounds__(WAVE) void k_simulate(DevModel md, DevSim sp, DevSt
     if (threadIdx.x < D)
         s.tau[threadIdx.x] = threadIdx.x < Dr ? st.torques_in[(size_t)Dr * e + threadIdx.x] : 0.f;
     __syncthreads();
-    substep<D, B, ROWS, CH, 1, PAD>(&s, mc, md, sp, st.added_mass ? st.added_mass[e] : 0.f, st.friction ? st.friction[e] : 1.f);
+    substep<D, B, ROWS, CH, 1, PAD>(&s, mc, md, sp, st.added_mass ? st.added_mass[e] : 0.f, st.friction ? st.friction[e] : 1.f, true);
     store_state<D, B, ROWS, 1, PAD>(s, st, md, e);
     if (st.rbs) body_states<D, B, ROWS, 1>(s, mc, st.rbs + (size_t)13 * Br * e, Br);
 }
@@ -1748,129 +1801,184 @@ __device__ __forceinline__ void resample_commands(const lgs_task_params& T, floa
 // ------------------------------------------------ post-physics (scalar) ----
 // legged_robot.py:673-709 with _post_physics_step_callback, check_termination,
 // compute_reward; humanoid variants h1_env.py / g1_env.py.  Everything up to
-// the reset decision; returns the reset flag in s.flags[0].  Called by all lanes:
-// lane 0 derives the base-frame state, commands and termination; then lane k
-// evaluates reward term k (all terms at once); lane 0 sums them in the reference's
-// (alphabetical) order, the same arithmetic as one lane summing term by term.
-template <int D, int B, int ROWS, bool PAD = false>
-__device__ __forceinline__ float reward_term(Smem<D, B, ROWS>& s, const lgs_task_params& T, const lgs_env_buffers& E,
-                                             const float* rbs, int e, int id) {
-    const int A = T.num_actions;
-    const float* root = s.root;
-    const float* bl = s.u.post.misc;
-    const float* ba = s.u.post.misc + 3;
-    const float* pg = s.u.post.misc + 6;
-    const float* leg_phase = s.u.post.misc + 10;
-    const float* cmd = s.u.post.misc + 12;
-    const float* act = s.act;
-    const float* last_act = E.last_actions + A * e;
-    const float* last_qd = E.last_dof_vel + (PAD ? A : D) * e;
-    float* air = E.feet_air_time + T.num_feet * e;
-    uint8_t* lastc = E.last_contacts + T.num_feet * e;
-    const float* tau = s.tau;
-    float sum = 0.f, r;
+// the reset decision; returns the reset flag in s.flags[0].  Called by all lanes.
+// Nothing here runs as a loop on one lane: the base-frame vectors, the Euler angles, the
+// heading, the commands, the gait phase and the termination forces each have a lane, and
+// the reward terms are evaluated in two stages (below).  Every element keeps the
+// reference's own arithmetic and every sum its index order, so the bits are those of one
+// lane looping.  The env's inputs come from s.pre (fetched with the state).
+
+// episode_length % interval == 0; the counter is int64 in the env buffers, and the 64-bit
+// remainder is a long software routine: a value below 2^31 takes the 32-bit one
+__device__ __forceinline__ bool ep_multiple(long long ep, int interval) {
+    if ((unsigned long long)ep < 0x80000000ull && interval > 0) return (uint32_t)ep % (uint32_t)interval == 0u;
+    return ep % interval == 0;
+}
+
+// how many elements reward term `id` adds up (0: a closed-form term)
+__device__ __forceinline__ int reward_count(const lgs_task_params& T, int id) {
     switch (id) {
-    case LGS_REW_LIN_VEL_Z: r = bl[2] * bl[2]; break;
-    case LGS_REW_ANG_VEL_XY: r = ba[0] * ba[0] + ba[1] * ba[1]; break;
-    case LGS_REW_ORIENTATION: r = pg[0] * pg[0] + pg[1] * pg[1]; break;
-    case LGS_REW_BASE_HEIGHT: { float d = root[2] - T.base_height_target; r = d * d; } break;
-    case LGS_REW_TORQUES: for (int j = 0; j < A; ++j) sum += tau[j] * tau[j]; r = sum; break;
-    case LGS_REW_DOF_VEL: for (int j = 0; j < A; ++j) sum += s.qd[j] * s.qd[j]; r = sum; break;
-    case LGS_REW_DOF_ACC:
-        for (int j = 0; j < A; ++j) { float d = (last_qd[j] - s.qd[j]) / T.control_dt; sum += d * d; }
-        r = sum; break;
-    case LGS_REW_ACTION_RATE:
-        for (int j = 0; j < A; ++j) { float d = last_act[j] - act[j]; sum += d * d; }
-        r = sum; break;
-    case LGS_REW_COLLISION:
-        for (int i = 0; i < T.num_penalised; ++i) {
-            const float* F = s.cf[T.penalised_idx[i]];
-            sum += (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 0.1f) ? 1.f : 0.f;
-        }
-        r = sum; break;
-    case LGS_REW_DOF_POS_LIMITS:
-        for (int j = 0; j < A; ++j) {
-            float o = -fminf(s.q[j] - T.soft_dof_pos_lower[j], 0.f);
-            o += fmaxf(s.q[j] - T.soft_dof_pos_upper[j], 0.f);
-            sum += o;
-        }
-        r = sum; break;
-    case LGS_REW_DOF_VEL_LIMITS:
-        for (int j = 0; j < A; ++j) sum += clipf(fabsf(s.qd[j]) - T.dof_vel_limits[j] * T.soft_dof_vel_limit, 0.f, 1.f);
-        r = sum; break;
-    case LGS_REW_TORQUE_LIMITS:
-        for (int j = 0; j < A; ++j) sum += fmaxf(fabsf(tau[j]) - T.torque_limits[j] * T.soft_torque_limit, 0.f);
-        r = sum; break;
-    case LGS_REW_TRACKING_LIN_VEL: {
-        float e0 = cmd[0] - bl[0], e1 = cmd[1] - bl[1];
-        r = lgs_expf(-(e0 * e0 + e1 * e1) / T.tracking_sigma);
-    } break;
-    case LGS_REW_TRACKING_ANG_VEL: {
-        float d = cmd[2] - ba[2];
-        r = lgs_expf(-(d * d) / T.tracking_sigma);
-    } break;
-    case LGS_REW_FEET_AIR_TIME: {
-        int filt[LGS_MAX_FEET];
-        for (int f = 0; f < T.num_feet; ++f) {
-            int contact = s.cf[T.feet_idx[f]][2] > 1.f;
-            filt[f] = contact || lastc[f];
-            lastc[f] = (uint8_t)contact;
-            float first = (air[f] > 0.f && filt[f]) ? 1.f : 0.f;
-            air[f] += T.control_dt;
-            sum += (air[f] - 0.5f) * first;
-        }
-        float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]);
-        sum *= (cn > 0.1f) ? 1.f : 0.f;
-        for (int f = 0; f < T.num_feet; ++f)
-            if (filt[f]) air[f] = 0.f;
-        r = sum;
-    } break;
-    case LGS_REW_FEET_STUMBLE: {
-        r = 0.f;
-        for (int f = 0; f < T.num_feet; ++f) {
-            const float* F = s.cf[T.feet_idx[f]];
-            if (sqrtf(F[0] * F[0] + F[1] * F[1]) > 5.f * fabsf(F[2])) r = 1.f;
-        }
-    } break;
-    case LGS_REW_STAND_STILL: {
-        for (int j = 0; j < A; ++j) sum += fabsf(s.q[j] - T.default_dof_pos[j]);
-        float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]);
-        r = sum * ((cn < 0.1f) ? 1.f : 0.f);
-    } break;
-    case LGS_REW_FEET_CONTACT_FORCES:
-        for (int f = 0; f < T.num_feet; ++f) {
-            const float* F = s.cf[T.feet_idx[f]];
-            sum += fmaxf(sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) - T.max_contact_force, 0.f);
-        }
-        r = sum; break;
-    case LGS_REW_ALIVE: r = 1.0f; break;
-    case LGS_REW_CONTACT:
-        for (int f = 0; f < T.num_feet; ++f) {
-            int stance = leg_phase[f] < T.stance_threshold;
-            int contact = s.cf[T.feet_idx[f]][2] > 1.f;
-            sum += (contact == stance) ? 1.f : 0.f;
-        }
-        r = sum; break;
+    case LGS_REW_TORQUES: case LGS_REW_DOF_VEL: case LGS_REW_DOF_ACC: case LGS_REW_ACTION_RATE:
+    case LGS_REW_DOF_POS_LIMITS: case LGS_REW_DOF_VEL_LIMITS: case LGS_REW_TORQUE_LIMITS: case LGS_REW_STAND_STILL:
+        return T.num_actions;
+    case LGS_REW_COLLISION: return T.num_penalised;
+    case LGS_REW_FEET_AIR_TIME: case LGS_REW_FEET_STUMBLE: case LGS_REW_FEET_CONTACT_FORCES: case LGS_REW_CONTACT:
     case LGS_REW_FEET_SWING_HEIGHT:
-        for (int f = 0; f < T.num_feet; ++f) {
-            const float* F = s.cf[T.feet_idx[f]];
-            int contact = sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f;
-            float d = rbs[13 * T.feet_idx[f] + 2] - T.swing_height_target;
-            sum += d * d * (contact ? 0.f : 1.f);
+        return T.num_feet;
+    case LGS_REW_CONTACT_NO_VEL: return 3 * T.num_feet;
+    case LGS_REW_HIP_POS: return T.num_hip;
+    default: return 0;
+    }
+}
+
+// this lane's rows of the task's tables and of the env's state: read before the base-frame
+// block so that the one round trip of the table reads is not on the rewards' path
+struct RewardIn {
+    int id;                        // lane k: active term k (-1 beyond the last)
+    float scale;
+    float lo, hi, vlim, tlim, dflt;  // DOF lane
+    int fb, pb, hd, tb;            // foot / penalised / hip-DOF / termination lane: its body (DOF)
+};
+template <int EPW>
+__device__ __forceinline__ RewardIn reward_inputs(const lgs_task_params& T) {
+    const int lane = hl<EPW>();
+    RewardIn in;
+    const int kl = lane < T.num_rewards ? lane : 0;
+    in.id = T.reward_ids[kl];
+    in.scale = T.reward_scales[kl];
+    if (lane >= T.num_rewards) in.id = -1;
+    const int jl = lane < T.num_actions ? lane : 0;
+    in.lo = T.soft_dof_pos_lower[jl];
+    in.hi = T.soft_dof_pos_upper[jl];
+    in.vlim = T.dof_vel_limits[jl];
+    in.tlim = T.torque_limits[jl];
+    in.dflt = T.default_dof_pos[jl];
+    in.fb = T.num_feet > 0 ? T.feet_idx[lane < T.num_feet ? lane : 0] : 0;
+    in.pb = T.num_penalised > 0 ? T.penalised_idx[lane < T.num_penalised ? lane : 0] : 0;
+    in.hd = T.num_hip > 0 ? T.hip_dofs[lane < T.num_hip ? lane : 0] : 0;
+    const int ti = lane - 8;  // (the termination bodies' lanes, after the base-frame ones)
+    in.tb = (ti >= 0 && ti < T.num_termination) ? T.termination_idx[ti] : 0;
+    return in;
+}
+
+// Reward terms, two stages.  Stage one: for every active term k that is a sum over DOFs,
+// feet or contact bodies, lane j writes element j to el[k][j].  The term id is the same in
+// every lane (a readlane of lane k's id), so the switch is a scalar branch and no lane
+// diverges.  Stage two: lane k adds row k in index order -- the additions of the
+// reference's loop, in its order -- and the closed-form terms are short cases.
+// Returns term k (unscaled) on lane k.
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_task_params& T, const lgs_env_buffers& E,
+                                              const float* rbs, int e, const RewardIn& in) {
+    constexpr int EL = Smem<D, B, ROWS>::EL;
+    const int lane = hl<EPW>();
+    const int A = T.num_actions, nr = T.num_rewards, nf = T.num_feet;
+    const float* mi = s.u.post.misc;  // bl 0-2, ba 3-5, pg 6-8, phase 9, leg_phase 10-11, cmd 12-15
+    const int jl = lane < A ? lane : 0;
+    const float q = s.q[jl], qd = s.qd[jl], tau = s.tau[jl], act = s.act[jl];
+    const float last_act = s.pre.last_act[jl], last_qd = s.pre.last_qd[jl];
+    const float F0 = s.cf[in.fb][0], F1 = s.cf[in.fb][1], F2 = s.cf[in.fb][2];  // this lane's foot
+    for (int k = 0; k < nr; ++k) {
+        const int id = rli(in.id, k);  // (both envs of a wave have the same task)
+        float v = 0.f;
+        switch (id) {
+        case LGS_REW_TORQUES: v = tau * tau; break;
+        case LGS_REW_DOF_VEL: v = qd * qd; break;
+        case LGS_REW_DOF_ACC: { float d = (last_qd - qd) / T.control_dt; v = d * d; } break;
+        case LGS_REW_ACTION_RATE: { float d = last_act - act; v = d * d; } break;
+        case LGS_REW_COLLISION: {
+            const float* F = s.cf[in.pb];
+            v = (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 0.1f) ? 1.f : 0.f;
+        } break;
+        case LGS_REW_DOF_POS_LIMITS: {
+            float o = -fminf(q - in.lo, 0.f);
+            o += fmaxf(q - in.hi, 0.f);
+            v = o;
+        } break;
+        case LGS_REW_DOF_VEL_LIMITS: v = clipf(fabsf(qd) - in.vlim * T.soft_dof_vel_limit, 0.f, 1.f); break;
+        case LGS_REW_TORQUE_LIMITS: v = fmaxf(fabsf(tau) - in.tlim * T.soft_torque_limit, 0.f); break;
+        case LGS_REW_FEET_AIR_TIME:
+            if (lane < nf) {  // the feet are independent: each foot's update on its own lane
+                const int contact = F2 > 1.f;
+                const int filt = contact || s.pre.lastc[lane];
+                E.last_contacts[nf * e + lane] = (uint8_t)contact;
+                float air = s.pre.air[lane];
+                const float first = (air > 0.f && filt) ? 1.f : 0.f;
+                air += T.control_dt;
+                v = (air - 0.5f) * first;
+                E.feet_air_time[nf * e + lane] = filt ? 0.f : air;
+            }
+            break;
+        case LGS_REW_FEET_STUMBLE: v = (sqrtf(F0 * F0 + F1 * F1) > 5.f * fabsf(F2)) ? 1.f : 0.f; break;
+        case LGS_REW_STAND_STILL: v = fabsf(q - in.dflt); break;
+        case LGS_REW_FEET_CONTACT_FORCES:
+            v = fmaxf(sqrtf(F0 * F0 + F1 * F1 + F2 * F2) - T.max_contact_force, 0.f);
+            break;
+        case LGS_REW_CONTACT: {
+            const int stance = mi[10 + (lane < nf ? lane : 0)] < T.stance_threshold;
+            const int contact = F2 > 1.f;
+            v = (contact == stance) ? 1.f : 0.f;
+        } break;
+        case LGS_REW_FEET_SWING_HEIGHT:
+            if (lane < nf) {
+                const int contact = sqrtf(F0 * F0 + F1 * F1 + F2 * F2) > 1.f;
+                const float d = rbs[13 * in.fb + 2] - T.swing_height_target;
+                v = d * d * (contact ? 0.f : 1.f);
+            }
+            break;
+        case LGS_REW_CONTACT_NO_VEL:
+            if (lane < 3 * nf) {  // element 3 f + axis
+                const int f = lane / 3, k2 = lane - 3 * f, fb = T.feet_idx[f];
+                const float* F = s.cf[fb];
+                const float c = sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f ? 1.f : 0.f;
+                const float xx = rbs[13 * fb + 7 + k2] * c;
+                v = xx * xx;
+            }
+            break;
+        case LGS_REW_HIP_POS: v = s.q[in.hd] * s.q[in.hd]; break;
+        default: break;
         }
-        r = sum; break;
-    case LGS_REW_CONTACT_NO_VEL:
-        for (int f = 0; f < T.num_feet; ++f) {
-            const float* F = s.cf[T.feet_idx[f]];
-            float c = sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f ? 1.f : 0.f;
-            const float* vv = rbs + 13 * T.feet_idx[f] + 7;
-            for (int k2 = 0; k2 < 3; ++k2) { float xx = vv[k2] * c; sum += xx * xx; }
+        if (lane < reward_count(T, id)) s.u.post.el[k][lane] = v;
+    }
+    __syncthreads();
+    float r = 0.f;
+    if (lane < nr) {
+        const int cnt = reward_count(T, in.id);
+        float v[EL];
+#pragma unroll
+        for (int j = 0; j < EL; ++j) v[j] = s.u.post.el[lane][j];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < EL; ++j) sum = j < cnt ? sum + v[j] : sum;
+        const float* bl = mi;
+        const float* ba = mi + 3;
+        const float* pg = mi + 6;
+        const float* cmd = mi + 12;
+        float x = 0.f;  // the tracking terms' squared error
+        bool track = false;
+        switch (in.id) {
+        case LGS_REW_LIN_VEL_Z: r = bl[2] * bl[2]; break;
+        case LGS_REW_ANG_VEL_XY: r = ba[0] * ba[0] + ba[1] * ba[1]; break;
+        case LGS_REW_ORIENTATION: r = pg[0] * pg[0] + pg[1] * pg[1]; break;
+        case LGS_REW_BASE_HEIGHT: { float d = s.root[2] - T.base_height_target; r = d * d; } break;
+        case LGS_REW_TRACKING_LIN_VEL: {
+            float e0 = cmd[0] - bl[0], e1 = cmd[1] - bl[1];
+            x = e0 * e0 + e1 * e1; track = true;
+        } break;
+        case LGS_REW_TRACKING_ANG_VEL: { float d = cmd[2] - ba[2]; x = d * d; track = true; } break;
+        case LGS_REW_FEET_AIR_TIME: {
+            float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]);
+            r = sum * ((cn > 0.1f) ? 1.f : 0.f);
+        } break;
+        case LGS_REW_FEET_STUMBLE: r = sum > 0.f ? 1.f : 0.f; break;  // (any foot)
+        case LGS_REW_STAND_STILL: {
+            float cn = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]);
+            r = sum * ((cn < 0.1f) ? 1.f : 0.f);
+        } break;
+        case LGS_REW_ALIVE: r = 1.0f; break;
+        default: r = sum;
         }
-        r = sum; break;
-    case LGS_REW_HIP_POS:
-        for (int i = 0; i < T.num_hip; ++i) sum += s.q[T.hip_dofs[i]] * s.q[T.hip_dofs[i]];
-        r = sum; break;
-    default: r = 0.f;
+        if (track) r = lgs_expf(-x / T.tracking_sigma);
     }
     return r;
 }
@@ -1886,121 +1994,143 @@ template <int D, int B, int ROWS, int EPW, bool PAD = false>
 __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& T, const lgs_env_buffers& E,
                                     const float* rbs, int N, int e, uint32_t step, int part) {
     const int lane = hl<EPW>();
-    if (lane == 0 && part == PART_TERM_REWARDS) {
-        // the prepare part's results, as a Python callback may have left them
-        const int64_t ep = E.episode_length[e];
-        int reset = 0;
-        for (int i = 0; i < T.num_termination; ++i) {
-            const float* F = s.cf[T.termination_idx[i]];
-            if (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f) reset = 1;
+    const RewardIn in = reward_inputs<EPW>(T);
+    if (part == PART_TERM_REWARDS) {
+        if (lane == 0) {
+            // the prepare part's results, as a Python callback may have left them
+            const int64_t ep = s.pre.ep;
+            int reset = 0;
+            for (int i = 0; i < T.num_termination; ++i) {
+                const float* F = s.cf[T.termination_idx[i]];
+                if (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f) reset = 1;
+            }
+            if (fabsf(E.rpy[3 * e + 1]) > 1.0f || fabsf(E.rpy[3 * e]) > 0.8f) reset = 1;
+            const int timeout = (float)ep > T.max_episode_length;
+            reset |= timeout;
+            for (int i = 0; i < 3; ++i) {
+                s.u.post.misc[i] = E.base_lin_vel[3 * e + i];
+                s.u.post.misc[3 + i] = E.base_ang_vel[3 * e + i];
+                s.u.post.misc[6 + i] = E.projected_gravity[3 * e + i];
+            }
+            s.u.post.misc[9] = E.phase ? E.phase[e] : 0.f;
+            s.u.post.misc[10] = E.leg_phase ? E.leg_phase[2 * e] : 0.f;
+            s.u.post.misc[11] = E.leg_phase ? E.leg_phase[2 * e + 1] : 0.f;
+            for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = s.pre.cmd[i];
+            s.flags[0] = reset;
+            s.flags[1] = timeout;
         }
-        if (fabsf(E.rpy[3 * e + 1]) > 1.0f || fabsf(E.rpy[3 * e]) > 0.8f) reset = 1;
+    } else {
+        // lanes 0-2: base_lin_vel, base_ang_vel, projected_gravity; 3-5: roll, pitch, yaw;
+        // 6: the heading and the commands; 7: episode length and gait phase; 8..: one
+        // termination body each
+        const long long ep = s.pre.ep + 1;
+        const float* root = s.root;
+        const float* qt = root + 3;
+        bool term = false;
+        if (lane < 3) {
+            const int o = lane == 0 ? 7 : 10;
+            float v[3] = {root[o], root[o + 1], root[o + 2]}, w[3];
+            if (lane == 2) { v[0] = 0.f; v[1] = 0.f; v[2] = -1.f; }
+            quat_rotate_inverse(qt, v, w);
+            float* dst = (lane == 0 ? E.base_lin_vel : lane == 1 ? E.base_ang_vel : E.projected_gravity) + 3 * e;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { dst[i] = w[i]; s.u.post.misc[3 * lane + i] = w[i]; }
+        } else if (lane < 7) {
+            const float qx = qt[0], qy = qt[1], qz = qt[2], qw = qt[3];
+            float val;
+            if (lane == 4) {
+                float sinp = 2.0f * (qw * qy - qz * qx);
+                val = fabsf(sinp) >= 1.f ? copysignf(3.14159265358979323846f / 2.0f, sinp) : lgs_asinf(sinp);
+            } else {  // roll, yaw and the heading: one atan2 for the three lanes
+                float y, x;
+                if (lane == 3) {
+                    y = 2.0f * (qw * qx + qy * qz);
+                    x = qw * qw - qx * qx - qy * qy + qz * qz;
+                } else if (lane == 5) {
+                    y = 2.0f * (qw * qz + qx * qy);
+                    x = qw * qw + qx * qx - qy * qy - qz * qz;
+                } else {
+                    const float fx[3] = {1.f, 0.f, 0.f};
+                    float t[3], u[3];
+                    cross3(qt, fx, t);
+                    t[0] *= 2.f; t[1] *= 2.f; t[2] *= 2.f;
+                    cross3(qt, t, u);
+                    x = fx[0] + qt[3] * t[0] + u[0];
+                    y = fx[1] + qt[3] * t[1] + u[1];
+                }
+                val = lgs_atan2f(y, x);
+            }
+            if (lane < 6) {
+                E.rpy[3 * e + lane - 3] = val;
+                term = (lane == 3 && fabsf(val) > 0.8f) || (lane == 4 && fabsf(val) > 1.0f);
+            } else {
+                float cmd[4] = {s.pre.cmd[0], s.pre.cmd[1], s.pre.cmd[2], s.pre.cmd[3]};
+                if (ep_multiple(ep, T.resample_interval)) {
+                    resample_commands(T, cmd, T.seed, (uint32_t)e, step, LGS_STREAM_CMD);
+                    for (int i = 0; i < 4; ++i) E.commands[4 * e + i] = cmd[i];
+                }
+                if (T.heading_command) {
+                    const float tp = 2.0f * 3.14159265358979323846f;
+                    float wv = fmod_pos(cmd[3] - val, tp);
+                    if (wv > 3.14159265358979323846f) wv -= tp;
+                    cmd[2] = clipf(0.5f * wv, -1.f, 1.f);
+                    E.commands[4 * e + 2] = cmd[2];
+                }
+                for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = cmd[i];
+            }
+        } else if (lane == 7) {
+            E.episode_length[e] = ep;
+            s.pre.ep = ep;
+            float phase = 0.f, leg_phase[2] = {0.f, 0.f};
+            if (T.obs_layout == LGS_OBS_HUMANOID) {
+                float t = (float)ep * T.control_dt;
+                phase = fmod_pos(t, T.phase_period) / T.phase_period;
+                leg_phase[0] = phase;
+                leg_phase[1] = fmod_pos(phase + T.phase_offset, 1.0f);
+            }
+            s.u.post.misc[9] = phase;
+            s.u.post.misc[10] = leg_phase[0]; s.u.post.misc[11] = leg_phase[1];
+            if (E.phase) E.phase[e] = phase;
+            if (E.leg_phase) { E.leg_phase[2 * e] = leg_phase[0]; E.leg_phase[2 * e + 1] = leg_phase[1]; }
+        } else if (lane - 8 < T.num_termination) {
+            const float* F = s.cf[in.tb];
+            term = sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f;
+        }
         const int timeout = (float)ep > T.max_episode_length;
-        reset |= timeout;
-        for (int i = 0; i < 3; ++i) {
-            s.u.post.misc[i] = E.base_lin_vel[3 * e + i];
-            s.u.post.misc[3 + i] = E.base_ang_vel[3 * e + i];
-            s.u.post.misc[6 + i] = E.projected_gravity[3 * e + i];
-        }
-        s.u.post.misc[9] = E.phase ? E.phase[e] : 0.f;
-        s.u.post.misc[10] = E.leg_phase ? E.leg_phase[2 * e] : 0.f;
-        s.u.post.misc[11] = E.leg_phase ? E.leg_phase[2 * e + 1] : 0.f;
-        for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = E.commands[4 * e + i];
-        s.flags[0] = reset;
-        s.flags[1] = timeout;
-    } else if (lane == 0) {
-        float* root = s.root;
-        float* cmd = E.commands + 4 * e;
-        int64_t* ep = E.episode_length + e;
-        *ep += 1;
-        float bl[3], ba[3], pg[3], rpy[3];
-        const float g[3] = {0.f, 0.f, -1.f};
-        quat_rotate_inverse(root + 3, root + 7, bl);
-        quat_rotate_inverse(root + 3, root + 10, ba);
-        quat_rotate_inverse(root + 3, g, pg);
-        {
-            const float* q = root + 3;
-            float qx = q[0], qy = q[1], qz = q[2], qw = q[3];
-            float sinr = 2.0f * (qw * qx + qy * qz);
-            float cosr = qw * qw - qx * qx - qy * qy + qz * qz;
-            rpy[0] = lgs_atan2f(sinr, cosr);
-            float sinp = 2.0f * (qw * qy - qz * qx);
-            rpy[1] = fabsf(sinp) >= 1.f ? copysignf(3.14159265358979323846f / 2.0f, sinp) : lgs_asinf(sinp);
-            float siny = 2.0f * (qw * qz + qx * qy);
-            float cosy = qw * qw + qx * qx - qy * qy - qz * qz;
-            rpy[2] = lgs_atan2f(siny, cosy);
-        }
-        float phase = 0.f, leg_phase[2] = {0.f, 0.f};
-        if (T.obs_layout == LGS_OBS_HUMANOID) {
-            float t = (float)(*ep) * T.control_dt;
-            phase = fmod_pos(t, T.phase_period) / T.phase_period;
-            leg_phase[0] = phase;
-            leg_phase[1] = fmod_pos(phase + T.phase_offset, 1.0f);
-        }
-        const uint64_t seed = T.seed;
-        if ((*ep) % T.resample_interval == 0) resample_commands(T, cmd, seed, (uint32_t)e, step, LGS_STREAM_CMD);
-        if (T.heading_command) {
-            const float* q = root + 3;
-            const float fx[3] = {1.f, 0.f, 0.f};
-            float t[3], u[3];
-            cross3(q, fx, t);
-            t[0] *= 2.f; t[1] *= 2.f; t[2] *= 2.f;
-            cross3(q, t, u);
-            float fwd0 = fx[0] + q[3] * t[0] + u[0];
-            float fwd1 = fx[1] + q[3] * t[1] + u[1];
-            float heading = lgs_atan2f(fwd1, fwd0);
-            const float tp = 2.0f * 3.14159265358979323846f;
-            float wv = fmod_pos(cmd[3] - heading, tp);
-            if (wv > 3.14159265358979323846f) wv -= tp;
-            cmd[2] = clipf(0.5f * wv, -1.f, 1.f);
-        }
-        int reset = 0;
-        for (int i = 0; i < T.num_termination; ++i) {
-            const float* F = s.cf[T.termination_idx[i]];
-            if (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f) reset = 1;
-        }
-        if (fabsf(rpy[1]) > 1.0f || fabsf(rpy[0]) > 0.8f) reset = 1;
-        const int timeout = (float)(*ep) > T.max_episode_length;
-        reset |= timeout;
-        for (int i = 0; i < 3; ++i) {
-            E.base_lin_vel[3 * e + i] = bl[i];
-            E.base_ang_vel[3 * e + i] = ba[i];
-            E.projected_gravity[3 * e + i] = pg[i];
-            E.rpy[3 * e + i] = rpy[i];
-            s.u.post.misc[i] = bl[i]; s.u.post.misc[3 + i] = ba[i]; s.u.post.misc[6 + i] = pg[i];
-        }
-        s.u.post.misc[9] = phase;
-        s.u.post.misc[10] = leg_phase[0]; s.u.post.misc[11] = leg_phase[1];
-        for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = cmd[i];
-        if (E.phase) E.phase[e] = phase;
-        if (E.leg_phase) { E.leg_phase[2 * e] = leg_phase[0]; E.leg_phase[2 * e + 1] = leg_phase[1]; }
-        s.flags[0] = reset;
-        s.flags[1] = timeout;
+        const int reset = (hballot<EPW>(term) != 0ull) | timeout;
+        if (lane == 0) { s.flags[0] = reset; s.flags[1] = timeout; }
     }
     if (part == PART_PREPARE) return;  // (the base-frame state and commands are in E)
     __syncthreads();
-    // rewards: lane k evaluates active term k (alphabetical order, legged_robot.py:770-787)
+    STAMP(24);
+    // rewards: lane k holds active term k (alphabetical order, legged_robot.py:770-787)
+    float r = reward_terms<D, B, ROWS, EPW, PAD>(s, T, E, rbs, e, in);
     if (lane < T.num_rewards) {
-        const float r = reward_term<D, B, ROWS, PAD>(s, T, E, rbs, e, T.reward_ids[lane]) * T.reward_scales[lane];
-        s.u.post.terms[lane] = r;
-        E.episode_sums[(size_t)lane * N + e] += r;
+        r *= in.scale;
+        E.episode_sums[(size_t)lane * N + e] = s.pre.sums[lane] + r;
         if (E.rew_terms) E.rew_terms[(size_t)lane * N + e] = r;
     }
-    __syncthreads();
+    STAMP(25);
+    // the total, on every lane: the terms added in order (a broadcast each, no LDS round)
+    float rew = 0.f;
+#pragma unroll
+    for (int k = 0; k < LGS_MAX_REWARDS; ++k) {
+        const float rk = bc<EPW>(r, k);
+        rew = k < T.num_rewards ? rew + rk : rew;
+    }
     if (lane == 0) {
         const int reset = s.flags[0], timeout = s.flags[1];
-        float rew = 0.f;
-        for (int k = 0; k < T.num_rewards; ++k) rew += s.u.post.terms[k];
         if (T.only_positive_rewards && !T.defer_reward_total) rew = fmaxf(rew, 0.f);
         if (T.has_termination_reward && !T.defer_reward_total) {
-            float r = ((reset && !timeout) ? 1.f : 0.f) * T.termination_scale;
-            rew += r;
-            E.episode_sums[(size_t)T.num_rewards * N + e] += r;
+            float rt = ((reset && !timeout) ? 1.f : 0.f) * T.termination_scale;
+            rew += rt;
+            E.episode_sums[(size_t)T.num_rewards * N + e] = s.pre.sums[T.num_rewards] + rt;
         }
         E.rew[e] = rew;
         E.reset[e] = (uint8_t)reset;
         E.time_out[e] = (uint8_t)timeout;
     }
+    STAMP(26);
 }
 
 // episode-sum rows: native terms, termination, then the caller's (Python) terms
@@ -2078,42 +2208,49 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
             for (int k = lane; k < nsum; k += WAVE / EPW) E.episode_sums[(size_t)k * N + e] = 0.f;
         }
         if (lane == 0) {
-            resample_commands(T, E.commands + 4 * e, seed, (uint32_t)e, step, LGS_STREAM_RESET_CMD);
+            float* cmd = E.commands + 4 * e;
+            resample_commands(T, cmd, seed, (uint32_t)e, step, LGS_STREAM_RESET_CMD);
+            for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = cmd[i];  // (the observations' copy)
             E.episode_length[e] = 0;
+            s.pre.ep = 0;
         }
         __syncthreads();
     }
     if (force_reset) return;  // BaseTask.reset: the following step() builds obs
+    STAMP(27);
     // _push_robots (legged_robot.py:540-555)
-    if (lane == 0 && T.push_robots && E.episode_length[e] % T.push_interval == 0) {
+    if (lane == 0 && T.push_robots && ep_multiple(s.pre.ep, T.push_interval)) {
         s.root[7] = rand_range(-T.max_push_vel_xy, T.max_push_vel_xy, philox_uniform(seed, e, step, LGS_STREAM_PUSH, 0));
         s.root[8] = rand_range(-T.max_push_vel_xy, T.max_push_vel_xy, philox_uniform(seed, e, step, LGS_STREAM_PUSH, 1));
         if (pushed) atomicOr(pushed + (step & 1u), 1u);  // (few envs per step: the pushed and the reset ones)
     }
-    // compute_observations
-    if (lane == 0) {
-        const float* cmd = E.commands + 4 * e;
+    // compute_observations: entry i of the row on lane i
+    {
         // quadruped obs = tmp[0:O]; humanoid priv = tmp[0:P], obs = tmp[3:3+O]
         float* tmp = s.u.post.obs_tmp;
-        tmp[0] = s.u.post.misc[0] * T.obs_scale_lin_vel;
-        tmp[1] = s.u.post.misc[1] * T.obs_scale_lin_vel;
-        tmp[2] = s.u.post.misc[2] * T.obs_scale_lin_vel;
-        int k = 3;
-        for (int i = 0; i < 3; ++i) tmp[k++] = s.u.post.misc[3 + i] * T.obs_scale_ang_vel;
-        for (int i = 0; i < 3; ++i) tmp[k++] = s.u.post.misc[6 + i];
-        for (int i = 0; i < 3; ++i) tmp[k++] = cmd[i] * T.commands_scale[i];
-        for (int j = 0; j < Ad; ++j) tmp[k++] = (s.q[j] - T.default_dof_pos[j]) * T.obs_scale_dof_pos;
-        for (int j = 0; j < Ad; ++j) tmp[k++] = s.qd[j] * T.obs_scale_dof_vel;
-        for (int j = 0; j < Ad; ++j) tmp[k++] = act[j];
-        if (T.obs_layout == LGS_OBS_HUMANOID) {
-            float ph = 2.0f * 3.14159265358979323846f * s.u.post.misc[9];
-            float sp_, cp_;
-            lgs_sincosf(ph, &sp_, &cp_);
-            tmp[k++] = sp_;
-            tmp[k++] = cp_;
+        const float* mi = s.u.post.misc;
+        const bool hum = T.obs_layout == LGS_OBS_HUMANOID;
+        const int K = 12 + 3 * Ad + (hum ? 2 : 0);
+        for (int i = lane; i < K; i += WAVE / EPW) {
+            float v;
+            if (i < 3) v = mi[i] * T.obs_scale_lin_vel;
+            else if (i < 6) v = mi[i] * T.obs_scale_ang_vel;
+            else if (i < 9) v = mi[i];
+            else if (i < 12) v = mi[12 + (i - 9)] * T.commands_scale[i - 9];
+            else if (i < 12 + Ad) v = (s.q[i - 12] - T.default_dof_pos[i - 12]) * T.obs_scale_dof_pos;
+            else if (i < 12 + 2 * Ad) v = s.qd[i - 12 - Ad] * T.obs_scale_dof_vel;
+            else if (i < 12 + 3 * Ad) v = act[i - 12 - 2 * Ad];
+            else {
+                float ph = 2.0f * 3.14159265358979323846f * mi[9];
+                float sp_, cp_;
+                lgs_sincosf(ph, &sp_, &cp_);
+                v = i == K - 2 ? sp_ : cp_;
+            }
+            tmp[i] = v;
         }
     }
     __syncthreads();
+    STAMP(28);
     const int O = T.num_obs, P = T.num_privileged_obs;
     const int off = (T.obs_layout == LGS_OBS_HUMANOID) ? 3 : 0;
     for (int i = lane; i < O; i += WAVE / EPW) {
@@ -2163,6 +2300,11 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
     STAMP_BEGIN();
     __shared__ Smem<D, B, ROWS> sm[EPW];
     __shared__ ModelCache<D, B> mc;
+#ifndef LGS_PHASE_STAMPS
+    // the two-env variants keep 8 workgroups per CU (160 KB of LDS): 20 KB each, s.pre included
+    static_assert(EPW != 2 || EPW * sizeof(Smem<D, B, ROWS>) + sizeof(ModelCache<D, B>) <= 20 * 1024,
+                  "k_step: LDS per workgroup above 20 KB");
+#endif
     if (E.step_counter) step = (uint32_t)*E.step_counter;
     // the step key whose parity indexes this step's push flag, for a deferred step's consumer
     // (lgs_step_deferred: the consumer advances the counter, so it cannot read the key there)
@@ -2183,6 +2325,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
     __syncthreads();
 #endif
     load_state<D, B, ROWS, EPW, PAD>(s, st, md, e);
+    load_post_inputs<D, B, ROWS, EPW, PAD>(s, T, E, N, e, mode != MODE_PHYSICS);
     const int A = T.num_actions;
     const int Ad = PAD ? A : D, Br = PAD ? md.Br : B;  // (unpadded: compile-time bounds)
     float* rbs = (T.write_body_states && st.rbs) ? st.rbs + (size_t)13 * Br * e : nullptr;
@@ -2195,7 +2338,6 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
             E.actions[A * e + lane] = a;
             s.act[lane] = a;
         }
-        const float lqd = (lane < Ad) ? E.last_dof_vel[Ad * e + lane] : 0.f;
         const float am = st.added_mass ? st.added_mass[e] : 0.f;
         const float mu = st.friction ? st.friction[e] : 1.f;
         __syncthreads();
@@ -2205,13 +2347,17 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
                 const float q = s.q[lane], qd = s.qd[lane];
                 float t;
                 if (T.control_type == 0) t = T.p_gains[lane] * (as + T.default_dof_pos[lane] - q) - T.d_gains[lane] * qd;
-                else if (T.control_type == 1) t = T.p_gains[lane] * (as - qd) - T.d_gains[lane] * (qd - lqd) / sp.dt;
+                else if (T.control_type == 1) {
+                    const float lqd = lane < Ad ? s.pre.last_qd[lane] : 0.f;
+                    t = T.p_gains[lane] * (as - qd) - T.d_gains[lane] * (qd - lqd) / sp.dt;
+                }
                 else t = as;
                 s.tau[lane] = clipf(t, -T.torque_limits[lane], T.torque_limits[lane]);
             }
             __syncthreads();
 #ifndef LGS_DIAG_IO_ONLY
-            substep<D, B, ROWS, CH, EPW, PAD>(sm, mc, md, sp, am, mu);
+            // (only the last substep's contact forces are read: termination, rewards, store_state)
+            substep<D, B, ROWS, CH, EPW, PAD>(sm, mc, md, sp, am, mu, it == T.decimation - 1);
 #else
             // diagnostic build (never the shipped library): no physics, the step's global loads
             // and stores unchanged -- a known-byte calibration of the traffic counters
