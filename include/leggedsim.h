@@ -146,7 +146,8 @@ typedef struct lgs_self_collision_desc {
 /* ---- task (env) parameters: everything post_physics_step reads from cfg ---- */
 enum lgs_obs_layout {
     LGS_OBS_QUADRUPED = 0,   /* legged_robot.py:800-807  [v*s, w*s, g, cmd*s, dq, qd*s, a]          */
-    LGS_OBS_HUMANOID = 1     /* h1_env.py:68-95 / g1_env.py:108-141  obs=[w,g,cmd,dq,qd,a,sin,cos], priv=[v, obs] */
+    LGS_OBS_HUMANOID = 1,    /* h1_env.py:68-95 / g1_env.py:108-141  obs=[w,g,cmd,dq,qd,a,sin,cos], priv=[v, obs] */
+    LGS_OBS_HANDSTAND = 2    /* go2_handstand_env.py:140-173  obs = priv = [w*s, g, dq*s, qd*s, a, front flags, hind flags] */
 };
 
 /* reward term ids; the task lists the active ones in alphabetical order
@@ -158,6 +159,11 @@ enum lgs_reward_id {
     LGS_REW_FEET_CONTACT_FORCES, LGS_REW_FEET_STUMBLE, LGS_REW_FEET_SWING_HEIGHT,
     LGS_REW_HIP_POS, LGS_REW_LIN_VEL_Z, LGS_REW_ORIENTATION, LGS_REW_STAND_STILL,
     LGS_REW_TORQUE_LIMITS, LGS_REW_TORQUES, LGS_REW_TRACKING_ANG_VEL, LGS_REW_TRACKING_LIN_VEL,
+    /* the Go2 handstand task (go2_handstand_env.py:224-383); its `orientation` and `base_height`
+     * are its own formulas, so they have ids of their own (leggedsim/cabi.py, per-task aliases) */
+    LGS_REW_HANDSTAND_ORIENTATION, LGS_REW_HANDSTAND_BASE_HEIGHT, LGS_REW_FRONT_FEET_CONTACT,
+    LGS_REW_HIND_FEET_NO_CONTACT, LGS_REW_POSE, LGS_REW_STABILITY, LGS_REW_STAY_STILL, LGS_REW_LIN_VEL_XY,
+    LGS_REW_ENERGY, LGS_REW_FRONT_HIP_NEUTRAL, LGS_REW_FRONT_FEET_TOGETHER,
     LGS_REW_COUNT
 };
 
@@ -225,6 +231,32 @@ typedef struct lgs_task_params {
      * body b; the humanoid tasks: their feet, the only rows h1_env.py:34-52 reads); 0 = every body.
      * lgs_forward_kinematics (refresh_rigid_body_state_tensor) always refreshes every body. */
     uint32_t body_state_mask;
+    /* ---- task switches first used by the Go2 handstand task; all 0 = the behaviour above ---- */
+    /* P control: the PD target action * action_scale + default_dof_pos[j] is clipped to
+     * [pd_target_lower[j], pd_target_upper[j]] before the PD law, in every substep
+     * (go2_handstand_env.py:326-350; -inf / +inf leave a DOF free) */
+    int32_t clamp_pd_targets;
+    float pd_target_lower[LGS_MAX_DOFS], pd_target_upper[LGS_MAX_DOFS];
+    /* 1: env->torques, and what the torques / energy / torque_limits terms read, is the last
+     * substep's PD torque BEFORE the effort clip (the reference's self.torques when a task's
+     * _compute_torques does not clip, go2_handstand_env.py:349-350).  The joints are driven by the
+     * clipped torque either way. */
+    int32_t record_unclipped_torques;
+    /* check_termination: 0 = contact on a termination body, |roll| > 0.8, |pitch| > 1.0, time-out
+     * (legged_robot.py:711-721); 1 = contact, -fallen_band < projected_gravity.z < fallen_band,
+     * time-out (go2_handstand_env.py:178-219) */
+    int32_t termination_mode;
+    float fallen_band;
+    /* the `pose` term: (q - pose_target)^2 summed in DOF order over the DOFs of weight 1, then
+     * over the others of non-zero weight; weight-1 sum + w * other sum (w: the others' weight) */
+    float pose_target[LGS_MAX_DOFS], pose_weight[LGS_MAX_DOFS];
+    /* feet_idx[0 .. num_front_feet) are the front feet, the rest the hind feet */
+    int32_t num_front_feet;
+    /* contact flags (the LGS_OBS_HANDSTAND observation, front_feet_contact, hind_feet_no_contact):
+     * contact force z > contact_flag_threshold; with add_noise, observed flag j flips with
+     * probability contact_flip_prob (LGS_STREAM_NOISE draw num_obs + j) */
+    float contact_flag_threshold, contact_flip_prob;
+    float feet_together_target;    /* front_feet_together: xy distance of the two front feet allowed */
 } lgs_task_params;
 
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */

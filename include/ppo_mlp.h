@@ -311,7 +311,8 @@ PMLP_API int pmlp_permutation(int64_t* out, int64_t n, uint64_t seed, void* stre
 /* The whole forward of 4-layer Linear/ELU MLPs (rsl_rl's actor and critic) in ONE launch
  * (PPO.act's policy inference, the update's forward): per job
  *   y0 = ELU(x W0^T + b0), y1 = ELU(y0 W1^T + b1), y2 = ELU(y1 W2^T + b2), out = y2 W3^T + b3
- * with x fp32 (row m = x[rows ? rows[m] : m], columns >= kx read as 0, converted to bf16),
+ * with x fp32 (row m = x[rows ? rows[m] : m], columns >= kx read as 0, converted to bf16;
+ * ldx a multiple of 4 and x 16-byte aligned: 16-byte loads, any other ldx: by element),
  * bf16 W[l] = [N[l], K_l] (K_0 = K0, K_l = N[l-1]), fp32 b and out; the activations stay on
  * chip (LDS) between layers.  Optional stores: xa = the bf16 input rows [M, K0] and y[l] = the
  * bf16 hidden outputs (the backward's operands).  Bitwise equal to the per-layer pmlp_gemm

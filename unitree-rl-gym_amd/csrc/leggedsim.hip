@@ -1821,6 +1821,10 @@ __device__ __forceinline__ int reward_count(const lgs_task_params& T, int id) {
     case LGS_REW_TORQUES: case LGS_REW_DOF_VEL: case LGS_REW_DOF_ACC: case LGS_REW_ACTION_RATE:
     case LGS_REW_DOF_POS_LIMITS: case LGS_REW_DOF_VEL_LIMITS: case LGS_REW_TORQUE_LIMITS: case LGS_REW_STAND_STILL:
         return T.num_actions;
+    case LGS_REW_POSE: case LGS_REW_ENERGY: return T.num_actions;
+    case LGS_REW_FRONT_FEET_CONTACT: return T.num_front_feet;
+    case LGS_REW_HIND_FEET_NO_CONTACT: return T.num_feet - T.num_front_feet;
+    case LGS_REW_FRONT_HIP_NEUTRAL: return T.num_hip;
     case LGS_REW_COLLISION: return T.num_penalised;
     case LGS_REW_FEET_AIR_TIME: case LGS_REW_FEET_STUMBLE: case LGS_REW_FEET_CONTACT_FORCES: case LGS_REW_CONTACT:
     case LGS_REW_FEET_SWING_HEIGHT:
@@ -1936,6 +1940,15 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
             }
             break;
         case LGS_REW_HIP_POS: v = s.q[in.hd] * s.q[in.hd]; break;
+        // the handstand task's element terms (go2_handstand_env.py:248-358)
+        case LGS_REW_FRONT_HIP_NEUTRAL: v = s.q[in.hd] * s.q[in.hd]; break;
+        case LGS_REW_FRONT_FEET_CONTACT: v = F2 > T.contact_flag_threshold ? 1.f : 0.f; break;
+        case LGS_REW_HIND_FEET_NO_CONTACT: {  // element j: hind foot j (after the front feet)
+            const int f = T.num_front_feet + lane;
+            v = s.cf[T.feet_idx[f < nf ? f : 0]][2] > T.contact_flag_threshold ? 1.f : 0.f;
+        } break;
+        case LGS_REW_POSE: { const float d = q - T.pose_target[jl]; v = d * d; } break;
+        case LGS_REW_ENERGY: v = fabsf(tau) * fabsf(qd); break;
         default: break;
         }
         if (lane < reward_count(T, id)) s.u.post.el[k][lane] = v;
@@ -1976,6 +1989,49 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
             r = sum * ((cn < 0.1f) ? 1.f : 0.f);
         } break;
         case LGS_REW_ALIVE: r = 1.0f; break;
+        // the handstand task (go2_handstand_env.py:224-383)
+        case LGS_REW_HANDSTAND_ORIENTATION: {
+            const float err = 1.0f - clipf(pg[2], -1.0f, 1.0f);
+            r = lgs_expf(-3.0f * err * err);
+        } break;
+        case LGS_REW_HANDSTAND_BASE_HEIGHT: {
+            const float err = fmaxf(T.base_height_target - s.root[2], 0.f);
+            r = lgs_expf(-8.0f * err * err);
+        } break;
+        case LGS_REW_FRONT_FEET_CONTACT: r = sum / (float)cnt; break;  // (the mean over the front feet)
+        case LGS_REW_HIND_FEET_NO_CONTACT: r = 1.0f - sum / (float)cnt; break;
+        case LGS_REW_POSE: {
+            // the weight-1 (front) DOFs' squared errors in DOF order, then the others' (hind)
+            float front = 0.f, hind = 0.f, w = 0.f;
+#pragma unroll
+            for (int j = 0; j < EL; ++j)
+                if (j < cnt && T.pose_weight[j < LGS_MAX_DOFS ? j : 0] == 1.0f) front += v[j];
+#pragma unroll
+            for (int j = 0; j < EL; ++j) {
+                const float wj = T.pose_weight[j < LGS_MAX_DOFS ? j : 0];
+                if (j < cnt && wj != 1.0f && wj != 0.f) { hind += v[j]; w = wj; }
+            }
+            r = lgs_expf(-4.0f * (front + w * hind));
+        } break;
+        case LGS_REW_STABILITY: {
+            const float lin = sqrtf(bl[0] * bl[0] + bl[1] * bl[1]), ang = sqrtf(ba[0] * ba[0] + ba[1] * ba[1]);
+            r = lgs_expf(-2.0f * (lin + 0.5f * ang));
+        } break;
+        case LGS_REW_STAY_STILL: {
+            const float a = sqrtf(bl[0] * bl[0] + bl[1] * bl[1]) / 0.05f, b = fabsf(ba[2]) / 0.2f;
+            r = lgs_expf(-(a * a) - b * b);
+        } break;
+        case LGS_REW_LIN_VEL_XY: r = sqrtf(bl[0] * bl[0] + bl[1] * bl[1]); break;
+        case LGS_REW_FRONT_HIP_NEUTRAL: r = lgs_expf(-4.0f * sum); break;
+        case LGS_REW_FRONT_FEET_TOGETHER:
+            if (rbs && nf >= 2) {  // the two front feet's rows of rigid_body_states (this step's)
+                const float* fl = rbs + 13 * T.feet_idx[0];
+                const float* fr = rbs + 13 * T.feet_idx[1];
+                const float dx = fl[0] - fr[0], dy = fl[1] - fr[1];
+                const float err = fmaxf(sqrtf(dx * dx + dy * dy) - T.feet_together_target, 0.f);
+                r = lgs_expf(-20.0f * err * err);
+            }
+            break;
         default: r = sum;
         }
         if (track) r = lgs_expf(-x / T.tracking_sigma);
@@ -2004,7 +2060,10 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
                 const float* F = s.cf[T.termination_idx[i]];
                 if (sqrtf(F[0] * F[0] + F[1] * F[1] + F[2] * F[2]) > 1.f) reset = 1;
             }
-            if (fabsf(E.rpy[3 * e + 1]) > 1.0f || fabsf(E.rpy[3 * e]) > 0.8f) reset = 1;
+            if (T.termination_mode == 1) {  // (go2_handstand_env.py:211-212: neither upright nor inverted)
+                const float gz = E.projected_gravity[3 * e + 2];
+                if (gz > -T.fallen_band && gz < T.fallen_band) reset = 1;
+            } else if (fabsf(E.rpy[3 * e + 1]) > 1.0f || fabsf(E.rpy[3 * e]) > 0.8f) reset = 1;
             const int timeout = (float)ep > T.max_episode_length;
             reset |= timeout;
             for (int i = 0; i < 3; ++i) {
@@ -2035,6 +2094,8 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
             float* dst = (lane == 0 ? E.base_lin_vel : lane == 1 ? E.base_ang_vel : E.projected_gravity) + 3 * e;
 #pragma unroll
             for (int i = 0; i < 3; ++i) { dst[i] = w[i]; s.u.post.misc[3 * lane + i] = w[i]; }
+            // termination mode 1: the gravity lane decides "fallen" (go2_handstand_env.py:211-212)
+            term = T.termination_mode == 1 && lane == 2 && w[2] > -T.fallen_band && w[2] < T.fallen_band;
         } else if (lane < 7) {
             const float qx = qt[0], qy = qt[1], qz = qt[2], qw = qt[3];
             float val;
@@ -2062,7 +2123,7 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
             }
             if (lane < 6) {
                 E.rpy[3 * e + lane - 3] = val;
-                term = (lane == 3 && fabsf(val) > 0.8f) || (lane == 4 && fabsf(val) > 1.0f);
+                term = T.termination_mode == 0 && ((lane == 3 && fabsf(val) > 0.8f) || (lane == 4 && fabsf(val) > 1.0f));
             } else {
                 float cmd[4] = {s.pre.cmd[0], s.pre.cmd[1], s.pre.cmd[2], s.pre.cmd[3]};
                 if (ep_multiple(ep, T.resample_interval)) {
@@ -2230,10 +2291,20 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         float* tmp = s.u.post.obs_tmp;
         const float* mi = s.u.post.misc;
         const bool hum = T.obs_layout == LGS_OBS_HUMANOID;
-        const int K = 12 + 3 * Ad + (hum ? 2 : 0);
+        const bool hand = T.obs_layout == LGS_OBS_HANDSTAND;
+        const int K = hand ? 6 + 3 * Ad + T.num_feet : 12 + 3 * Ad + (hum ? 2 : 0);
         for (int i = lane; i < K; i += WAVE / EPW) {
             float v;
-            if (i < 3) v = mi[i] * T.obs_scale_lin_vel;
+            if (hand) {  // go2_handstand_env.py:140-154: [w*s, g, dq*s, qd*s, a, front flags, hind flags]
+                if (i < 3) v = mi[3 + i] * T.obs_scale_ang_vel;
+                else if (i < 6) v = mi[3 + i];
+                else if (i < 6 + Ad) v = (s.q[i - 6] - T.default_dof_pos[i - 6]) * T.obs_scale_dof_pos;
+                else if (i < 6 + 2 * Ad) v = s.qd[i - 6 - Ad] * T.obs_scale_dof_vel;
+                else if (i < 6 + 3 * Ad) v = act[i - 6 - 2 * Ad];
+                else  // the last substep's contact forces (a reset does not refresh them)
+                    v = s.cf[T.feet_idx[i - 6 - 3 * Ad]][2] > T.contact_flag_threshold ? 1.f : 0.f;
+            }
+            else if (i < 3) v = mi[i] * T.obs_scale_lin_vel;
             else if (i < 6) v = mi[i] * T.obs_scale_ang_vel;
             else if (i < 9) v = mi[i];
             else if (i < 12) v = mi[12 + (i - 9)] * T.commands_scale[i - 9];
@@ -2256,6 +2327,17 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
     for (int i = lane; i < O; i += WAVE / EPW) {
         float x = s.u.post.obs_tmp[off + i];
         if (T.add_noise) x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, i) - 1.f) * T.noise_vec[i];
+        if (T.obs_layout == LGS_OBS_HANDSTAND) {
+            // a contact flag flips with probability contact_flip_prob (go2_handstand_env.py:157-169);
+            // the privileged row is the noisy one (:172)
+            const int j = i - (O - T.num_feet);
+            if (T.add_noise && j >= 0) {
+                const bool flip = philox_uniform(seed, e, step, LGS_STREAM_NOISE, O + j) < T.contact_flip_prob;
+                x = ((x > 0.5f) != flip) ? 1.f : 0.f;
+            }
+            if (P > 0 && E.priv_obs && i < P)
+                E.priv_obs[(size_t)P * e + i] = clipf(x, -T.clip_observations, T.clip_observations);
+        }
         E.obs[(size_t)O * e + i] = clipf(x, -T.clip_observations, T.clip_observations);
     }
     if (P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID)
@@ -2341,17 +2423,23 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
         const float am = st.added_mass ? st.added_mass[e] : 0.f;
         const float mu = st.friction ? st.friction[e] : 1.f;
         __syncthreads();
+        float traw = 0.f;  // this DOF lane's PD torque before the effort clip (record_unclipped_torques)
         for (int it = 0; it < T.decimation; ++it) {  // :627-639
             if (lane < D) {  // _compute_torques :649-671
                 const float as = a * T.action_scale;
                 const float q = s.q[lane], qd = s.qd[lane];
                 float t;
-                if (T.control_type == 0) t = T.p_gains[lane] * (as + T.default_dof_pos[lane] - q) - T.d_gains[lane] * qd;
+                if (T.control_type == 0 && T.clamp_pd_targets) {  // the clamped target (go2_handstand_env.py:333-349)
+                    const float tg = clipf(as + T.default_dof_pos[lane], T.pd_target_lower[lane], T.pd_target_upper[lane]);
+                    t = T.p_gains[lane] * (tg - q) - T.d_gains[lane] * qd;
+                }
+                else if (T.control_type == 0) t = T.p_gains[lane] * (as + T.default_dof_pos[lane] - q) - T.d_gains[lane] * qd;
                 else if (T.control_type == 1) {
                     const float lqd = lane < Ad ? s.pre.last_qd[lane] : 0.f;
                     t = T.p_gains[lane] * (as - qd) - T.d_gains[lane] * (qd - lqd) / sp.dt;
                 }
                 else t = as;
+                traw = t;
                 s.tau[lane] = clipf(t, -T.torque_limits[lane], T.torque_limits[lane]);
             }
             __syncthreads();
@@ -2365,6 +2453,12 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
 #endif
         }
         STAMP(0);
+        if (T.record_unclipped_torques) {
+            // the joints were driven by the clipped torque; the task's torques buffer and its
+            // torque terms take the last substep's raw PD value (the reference's self.torques)
+            __syncthreads();
+            if (lane < D) s.tau[lane] = traw;
+        }
         if (lane < Ad) E.torques[Ad * e + lane] = s.tau[lane];
         // refresh_rigid_body_state (h1_env.py:49), humanoid tasks only: the rows they read
         if (rbs) body_states<D, B, ROWS, EPW>(s, mc, rbs, Br, T.body_state_mask);
@@ -3072,6 +3166,12 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
         if (t->termination_idx[i] < 0 || t->termination_idx[i] >= s->B) return set_err(LGS_ERR_ARG, "termination index out of range");
     for (int i = 0; i < t->num_hip; ++i)
         if (t->hip_dofs[i] < 0 || t->hip_dofs[i] >= s->D) return set_err(LGS_ERR_ARG, "hip dof out of range");
+    if (t->num_front_feet < 0 || t->num_front_feet > t->num_feet)
+        return set_err(LGS_ERR_ARG, "lgs_set_task: num_front_feet out of range");
+    if (t->termination_mode != 0 && t->termination_mode != 1)
+        return set_err(LGS_ERR_ARG, "lgs_set_task: unknown termination_mode");
+    if (t->obs_layout == LGS_OBS_HANDSTAND && t->num_obs != 6 + 3 * t->num_actions + t->num_feet)
+        return set_err(LGS_ERR_ARG, "lgs_set_task: the handstand layout has 6 + 3 A + num_feet observations");
     lgs_task_params tt = *t;  // a padded model's inert DOFs: no gains, no torque, no limits
     for (int j = t->num_actions; j < LGS_MAX_DOFS; ++j) {
         tt.p_gains[j] = tt.d_gains[j] = tt.default_dof_pos[j] = tt.torque_limits[j] = 0.f;

@@ -2113,7 +2113,7 @@ __global__ __launch_bounds__(FMLP_THREADS) void k_mlp_fwd(FmlpJobs jobs, int M, 
             for (int u = 0; u < 8; ++u) t[u] = (bf16)0.f;
             if (m < M) {
                 const float* src = J.x + (size_t)(J.rows ? J.rows[m] : (int64_t)m) * J.ldx + k;
-                if (k + 8 <= J.kx) {
+                if (k + 8 <= J.kx && (J.ldx & 3) == 0) {  // (16-byte rows: an odd width, e.g. 46, reads by element)
                     const float4 x0 = *(const float4*)src, x1 = *(const float4*)(src + 4);
                     t[0] = (bf16)x0.x; t[1] = (bf16)x0.y; t[2] = (bf16)x0.z; t[3] = (bf16)x0.w;
                     t[4] = (bf16)x1.x; t[5] = (bf16)x1.y; t[6] = (bf16)x1.z; t[7] = (bf16)x1.w;
@@ -2943,8 +2943,8 @@ static int fmlp_pack(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, Fml
     for (int i = 0; i < njobs; ++i) {
         const pmlp_mlp_fwd_job& J = jobs[i];
         const std::string w = "pmlp_mlp_forward job " + std::to_string(i) + ": ";
-        if (!J.x || J.kx <= 0 || J.ldx < J.kx || J.ldx % 4 || ((uintptr_t)J.x & 15))
-            return fail(-1, w + "x: 0 < kx <= ldx, ldx a multiple of 4, 16-byte aligned");
+        if (!J.x || J.kx <= 0 || J.ldx < J.kx || (J.ldx % 4 == 0 && ((uintptr_t)J.x & 15)) || ((uintptr_t)J.x & 3))
+            return fail(-1, w + "x: 0 < kx <= ldx, 16-byte aligned when ldx is a multiple of 4");
         if (J.K0 <= 0 || J.K0 % 16 || J.K0 > 64 || J.kx > J.K0)
             return fail(-1, w + "K0 must be a multiple of 16, kx <= K0 <= 64");
         if (J.xa && (J.ldxa < J.K0 || J.ldxa % 8 || !al16(J.xa))) return fail(-1, w + "xa: ldxa >= K0, a multiple of 8");

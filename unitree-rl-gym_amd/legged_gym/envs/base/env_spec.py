@@ -17,7 +17,9 @@ from legged_gym.utils.helpers import class_to_dict
 from leggedsim import cabi
 
 
-def derive_env_spec(cfg, model, sim_dt, obs_layout, hip_dof_indices=(), verbose=True):
+def derive_env_spec(cfg, model, sim_dt, obs_layout, hip_dof_indices=(), verbose=True, task_cls=None):
+    """task_cls: the task class, for what it adds to the spec on the host (its reward aliases,
+    its `extend_spec` constants); None: a plain LeggedRobot."""
     s = SimpleNamespace()
     s.cfg = cfg
     s.obs_layout = obs_layout
@@ -87,6 +89,10 @@ def derive_env_spec(cfg, model, sim_dt, obs_layout, hip_dof_indices=(), verbose=
             s.reward_scales[key] *= s.dt
     s.reward_names = [n for n in s.reward_scales if n != "termination"]
     s.sum_names = list(s.reward_names) + (["termination"] if "termination" in s.reward_scales else [])
+    s.reward_aliases = dict(getattr(task_cls, "reward_aliases", None) or {})
+    s.record_unclipped_torques = bool(getattr(task_cls, "record_unclipped_torques", False))
+    if hasattr(task_cls, "extend_spec"):
+        task_cls.extend_spec(s)
     return s
 
 
@@ -101,6 +107,12 @@ def noise_scale_vec(cfg, num_obs, A, obs_layout):
         v[6:9] = ns.gravity * lvl
         v[12:12 + A] = ns.dof_pos * lvl * sc.dof_pos
         v[12 + A:12 + 2 * A] = ns.dof_vel * lvl * sc.dof_vel
+    elif obs_layout == cabi.OBS_HANDSTAND:
+        # go2_handstand_env.py:386-423: gyro, gravity, dof pos, dof vel; actions and contact flags 0
+        v[:3] = lvl * ns.gyro * sc.ang_vel
+        v[3:6] = lvl * ns.gravity
+        v[6:6 + A] = lvl * ns.dof_pos * sc.dof_pos
+        v[6 + A:6 + 2 * A] = lvl * ns.dof_vel * sc.dof_vel
     else:
         v[:3] = ns.ang_vel * lvl * sc.ang_vel
         v[3:6] = ns.gravity * lvl

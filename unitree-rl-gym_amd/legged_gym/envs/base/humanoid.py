@@ -10,25 +10,10 @@ from .legged_robot import LeggedRobot
 _OWN_FEET = ("_feet_state", "_feet_pos", "_feet_vel")
 
 
-class HumanoidRobot(LeggedRobot):
-    obs_layout = cabi.OBS_HUMANOID
-    # 8 contact slots + 8 joint-limit rows = the 32-row variant, which runs two envs per
-    # wave (H1 8192: 0.70 -> 0.38 ms per control step).  Slot order (include/leggedsim.h):
-    # one slot per body on the ground first (a knee, hip or pelvis is never crowded out by
-    # the soles), then up to 4 self contacts, then further sole corners (the feet's
-    # candidates are dealt round-robin, Model.reorder_points: two planted soles share the
-    # rest evenly).  Limits beyond the 8 limit rows use the rows of unused contact slots.
-    max_contacts = 8
-    max_rows = 32
-    max_self_contacts = 4
-
-    def _init_buffers(self):
-        super()._init_buffers()
-        self._init_foot()
-
-    def _init_foot(self):
-        """h1_env.py:34-46: the feet's rows of the rigid body state tensor."""
-        self.feet_num = len(self.feet_indices)
+class FeetStateViews:
+    """feet_state / feet_pos / feet_vel over the feet rows of rigid_body_states that the step
+    refreshes (body_state_mask), for the tasks that read them: the humanoids and the Go2
+    handstand (go2_handstand_env.py:66-88).  Mixed in before LeggedRobot."""
 
     def update_feet_state(self):
         """h1_env.py:48-56 copies the feet rows after every step.  Here feet_state / feet_pos /
@@ -76,3 +61,24 @@ class HumanoidRobot(LeggedRobot):
     @feet_vel.setter
     def feet_vel(self, v):
         self.__dict__["_feet_vel"] = v
+
+
+class HumanoidRobot(FeetStateViews, LeggedRobot):
+    obs_layout = cabi.OBS_HUMANOID
+    # 8 contact slots + 8 joint-limit rows = the 32-row variant, which runs two envs per
+    # wave (H1 8192: 0.70 -> 0.38 ms per control step).  Slot order (include/leggedsim.h):
+    # one slot per body on the ground first (a knee, hip or pelvis is never crowded out by
+    # the soles), then up to 4 self contacts, then further sole corners (the feet's
+    # candidates are dealt round-robin, Model.reorder_points: two planted soles share the
+    # rest evenly).  Limits beyond the 8 limit rows use the rows of unused contact slots.
+    max_contacts = 8
+    max_rows = 32
+    max_self_contacts = 4
+
+    def _init_buffers(self):
+        super()._init_buffers()
+        self._init_foot()
+
+    def _init_foot(self):
+        """h1_env.py:34-46: the feet's rows of the rigid body state tensor."""
+        self.feet_num = len(self.feet_indices)

@@ -112,6 +112,11 @@ class LeggedRobot(BaseTask):
     # else "feet".  self.gym.refresh_rigid_body_state_tensor always refreshes every body.
     rigid_body_state_bodies = None
     hip_dof_indices = ()
+    # a task class's own names for terms the kernel has under another id (cabi.reward_id)
+    reward_aliases = {}
+    # True: self.torques (and the torque terms) hold the PD torque before the effort clip
+    # (lgs_task_params.record_unclipped_torques); the joints get the clipped torque either way
+    record_unclipped_torques = False
     max_contacts = 8
     max_rows = 32
     max_self_contacts = 4  # contact slots self contacts may take per substep (cfg.asset.self_collisions == 0)
@@ -175,7 +180,15 @@ class LeggedRobot(BaseTask):
                 "methods, so the override would be silently ignored.  Supported plugin points: cfg values, "
                 "Python `_reward_<name>` terms (scaled like the reference's), overrides of "
                 f"{', '.join(cls.PYTHON_STEP_HOOKS)} and _get_noise_scale_vec, and reset_idx(env_ids); "
-                "see INTEGRATION.md.")
+                "see INTEGRATION.md.  A _compute_torques override that only clamps the PD target per DOF is "
+                "native: return the bounds from _pd_target_limits().")
+
+    def _pd_target_limits(self):
+        """Per-DOF bounds on the P-control target `action * action_scale + default_dof_pos`, applied
+        inside the substep loop before the PD law: None (no clamp), or (lower, upper), each
+        [num_dof]; -inf / +inf leave a DOF free.  The native replacement for a `_compute_torques`
+        override that clamps targets (the reference's go2_handstand_env.py:326-350)."""
+        return None
 
     # ------------------------------------------------------------ config ----
     def _parse_cfg(self, cfg):
@@ -200,8 +213,10 @@ class LeggedRobot(BaseTask):
         model_feet = {model.body_names.index(n) for n in model.body_names if self.cfg.asset.foot_name in n}
         model.reorder_points(model_feet)
         self.model = model
-        spec = derive_env_spec(self.cfg, model, self.sim_params.dt, self.obs_layout, self.hip_dof_indices)
+        spec = derive_env_spec(self.cfg, model, self.sim_params.dt, self.obs_layout, self.hip_dof_indices,
+                               task_cls=type(self))
         self.spec = spec
+        self.hip_dof_indices = spec.hip_dof_indices
         dev = self.device
         self.num_dof = spec.num_dof
         self.num_bodies = spec.num_bodies
@@ -417,7 +432,7 @@ class LeggedRobot(BaseTask):
         self.reward_names = list(self.spec.reward_names)
         self._native_reward_names, self._py_rewards = [], []
         for n in self.reward_names:
-            if cabi.REWARD_ALIASES.get(n, n) in cabi.REWARD_ID:
+            if cabi.reward_id(n, self.reward_aliases) is not None:
                 self._native_reward_names.append(n)
             else:  # AttributeError like the reference's getattr (:834) when the task has no such method
                 self._py_rewards.append((n, getattr(self, "_reward_" + n)))

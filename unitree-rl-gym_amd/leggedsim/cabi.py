@@ -23,6 +23,7 @@ NUM_CONTACT_STATS = 3  # lgs_get_contact_stats: bodies without a slot, self cont
 
 OBS_QUADRUPED = 0
 OBS_HUMANOID = 1
+OBS_HANDSTAND = 2
 
 # lgs_reward_id, in the header's order
 REWARD_IDS = [
@@ -30,10 +31,23 @@ REWARD_IDS = [
     "dof_acc", "dof_pos_limits", "dof_vel", "dof_vel_limits", "feet_air_time", "feet_contact_forces",
     "feet_stumble", "feet_swing_height", "hip_pos", "lin_vel_z", "orientation", "stand_still",
     "torque_limits", "torques", "tracking_ang_vel", "tracking_lin_vel",
+    # the Go2 handstand task's terms
+    "handstand_orientation", "handstand_base_height", "front_feet_contact", "hind_feet_no_contact", "pose",
+    "stability", "stay_still", "lin_vel_xy", "energy", "front_hip_neutral", "front_feet_together",
 ]
 REWARD_ID = {n: i for i, n in enumerate(REWARD_IDS)}
 # the reference names the stumble term `_reward_stumble` but the cfg key is `feet_stumble`
 REWARD_ALIASES = {"stumble": "feet_stumble"}
+# per-task aliases (a task class's `reward_aliases`): the handstand class redefines two of the base
+# terms, so its cfg keys `orientation` / `base_height` name its own formulas
+HANDSTAND_REWARD_ALIASES = {"orientation": "handstand_orientation", "base_height": "handstand_base_height"}
+
+
+def reward_id(name, task_aliases=None):
+    """The lgs_reward_id of cfg reward key `name` for a task with `task_aliases`, or None when the
+    kernel has no such term (a Python `_reward_<name>` then)."""
+    name = (task_aliases or {}).get(name, name)
+    return REWARD_ID.get(REWARD_ALIASES.get(name, name))
 
 STREAM_NOISE, STREAM_CMD, STREAM_RESET_DOF, STREAM_RESET_ROOT, STREAM_RESET_CMD, STREAM_PUSH = range(6)
 
@@ -116,6 +130,14 @@ class TaskParams(C.Structure):
         ("custom_origins", C.c_int32),
         ("defer_reward_total", C.c_int32), ("num_extra_sums", C.c_int32),
         ("body_state_mask", C.c_uint32),
+        ("clamp_pd_targets", C.c_int32),
+        ("pd_target_lower", C.c_float * MAX_DOFS), ("pd_target_upper", C.c_float * MAX_DOFS),
+        ("record_unclipped_torques", C.c_int32),
+        ("termination_mode", C.c_int32), ("fallen_band", C.c_float),
+        ("pose_target", C.c_float * MAX_DOFS), ("pose_weight", C.c_float * MAX_DOFS),
+        ("num_front_feet", C.c_int32),
+        ("contact_flag_threshold", C.c_float), ("contact_flip_prob", C.c_float),
+        ("feet_together_target", C.c_float),
     ]
 
 

@@ -91,8 +91,9 @@ def build_task_params(env) -> cabi.TaskParams:
     # Python terms add to it or a Python check_termination decides the resets
     T.defer_reward_total = int(bool(py) or "check_termination" in hooks)
     T.num_extra_sums = len(py)
+    aliases = getattr(env, "reward_aliases", None)  # the task class's own names for native terms
     for k, n in enumerate(native):
-        T.reward_ids[k] = cabi.REWARD_ID[cabi.REWARD_ALIASES.get(n, n)]
+        T.reward_ids[k] = cabi.reward_id(n, aliases)
         T.reward_scales[k] = float(env.reward_scales[n])
     T.has_termination_reward = int("termination" in env.reward_scales)
     T.termination_scale = float(env.reward_scales.get("termination", 0.0))
@@ -123,4 +124,34 @@ def build_task_params(env) -> cabi.TaskParams:
     else:
         T.body_state_mask = sum(1 << b for b in fi) if fi else 0
     T.custom_origins = int(bool(getattr(env, "custom_origins", False)))
+    _native_task_switches(T, env, A)
     return T
+
+
+def _native_task_switches(T, env, A):
+    """The task switches past the base env's behaviour (all off for a plain LeggedRobot):
+    a per-DOF clamp of the PD target (LeggedRobot._pd_target_limits), and the handstand
+    task's constants (`handstand` namespace of the env spec, envs/go2/go2_handstand_env.py)."""
+    lim = env._pd_target_limits() if hasattr(env, "_pd_target_limits") else getattr(env, "pd_target_limits", None)
+    if lim is not None:
+        lo, hi = (_np(x).astype(np.float32).reshape(-1) for x in lim)
+        if len(lo) != A or len(hi) != A:
+            raise ValueError(f"_pd_target_limits must return two vectors of {A} entries")
+        if T.control_type != 0:
+            raise ValueError("_pd_target_limits needs control_type 'P' (the clamp is on the position target)")
+        T.clamp_pd_targets = 1
+        _put(T.pd_target_lower, lo)
+        _put(T.pd_target_upper, hi)
+    T.record_unclipped_torques = int(bool(getattr(env, "record_unclipped_torques", False)))
+    hs = getattr(env, "handstand", None)
+    if hs is None:
+        hs = getattr(getattr(env, "spec", None), "handstand", None)
+    if hs is not None:
+        T.termination_mode = 1
+        T.fallen_band = hs.fallen_band
+        _put(T.pose_target, hs.pose_target)
+        _put(T.pose_weight, hs.pose_weight)
+        T.num_front_feet = hs.num_front_feet
+        T.contact_flag_threshold = hs.contact_flag_threshold
+        T.contact_flip_prob = hs.contact_flip_prob
+        T.feet_together_target = hs.feet_together_target
