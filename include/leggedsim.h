@@ -257,7 +257,41 @@ typedef struct lgs_task_params {
      * probability contact_flip_prob (LGS_STREAM_NOISE draw num_obs + j) */
     float contact_flag_threshold, contact_flip_prob;
     float feet_together_target;    /* front_feet_together: xy distance of the two front feet allowed */
+    /* ---- rough-terrain switches; all 0 = the behaviour above ---- */
+    /* 1: an env that resets in a control step or in lgs_reset_idx first moves its terrain level
+     * (legged_gym's _update_terrain_curriculum; lgs_reset_all moves nothing), on its pre-reset root
+     * xy and commands, all comparisons on squares (fp32, in this order):
+     *   dx = x - ox; dy = y - oy; d2 = dx*dx + dy*dy            (ox, oy = env_origins[e])
+     *   up   = d2 > terrain_half_length_sq
+     *   h = 0.5f * max_episode_length_s
+     *   down = !up && d2 < (cx*cx + cy*cy) * (h*h)               (cx, cy = commands[e][0:2])
+     *   L = terrain_levels[e] + up - down
+     *   L = L >= terrain_rows ? min((int)(u * terrain_rows), terrain_rows - 1) : max(L, 0)
+     *   env_origins[e] = terrain_origins[L][terrain_types[e]]    (u: LGS_STREAM_TERRAIN draw 0)
+     * The root placement of the same reset reads the new origin.  Needs the env buffers
+     * terrain_levels, terrain_types and terrain_origins; terrain_level_sum is optional. */
+    int32_t terrain_curriculum;
+    int32_t terrain_rows, terrain_cols;   /* tile rows (levels) and columns (types) of terrain_origins */
+    float terrain_half_length_sq;         /* (terrain_length / 2)^2 */
+    /* 1: every control step fills env->measured_heights [N, P], P = num_height_x * num_height_y,
+     * point k = ix * num_height_y + iy, from the post-physics, pre-reset root state (where
+     * legged_gym's _post_physics_step_callback measures; legged_gym's _get_heights):
+     *   (z', w') = (qz, qw) / sqrt(qz*qz + qw*qw); c = w'*w' - z'*z'; s = 2 * w' * z'   (yaw only)
+     *   X = ((c*px - s*py) + x) + border_size;  Y = ((s*px + c*py) + y) + border_size
+     *   i = clip((int)(X / horizontal_scale), 0, rows - 2); j likewise with cols
+     *   height = min(H[i][j], H[i+1][j], H[i][j+1]) * vertical_scale        (0 on the plane) */
+    int32_t measure_heights;
+    int32_t num_height_x, num_height_y;   /* each <= LGS_MAX_HEIGHT_POINTS */
+    float height_points_x[32], height_points_y[32];
+    /* 1 (needs measure_heights): the height terms are relative to the ground.
+     *   base_height       = (mean_k(root_z - measured_heights[k]) - base_height_target)^2; the mean's
+     *                       order: partial j < 32 adds its points k = j, j + 32, ... in rising k
+     *                       from 0, the partials are added j = 0..31 from 0, divided by P;
+     *   feet_swing_height = ((foot_z - ground(foot_x, foot_y)) - swing_height_target)^2 off contact,
+     *                       ground = the triangle interpolation documented at lgs_set_heightfield. */
+    int32_t ground_relative_heights;
 } lgs_task_params;
+#define LGS_MAX_HEIGHT_POINTS 32
 
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */
 typedef struct lgs_env_buffers {
@@ -301,6 +335,17 @@ typedef struct lgs_env_buffers {
     /* optional [num_sums + 1]: the accumulator the NEXT control step adds into, when the caller
        alternates two episode_acc slots (lgs_step_deferred); the extras zero it with episode_acc */
     float* episode_acc_next;
+    /* ---- rough terrain (lgs_task_params terrain_curriculum / measure_heights); each may be NULL
+     *      when its switch is off ---- */
+    int64_t* terrain_levels;        /* [N] the env's level (tile row), live like episode_length */
+    const int64_t* terrain_types;   /* [N] the env's tile column */
+    const float* terrain_origins;   /* [terrain_rows, terrain_cols, 3] tile origins */
+    /* [1] the sum of terrain_levels over all envs, kept exact: a reset env adds its integer level
+     * change atomically.  When set (with ep_means), ep_means / ep_snapshot have one more trailing
+     * slot [num_sums]: the extras write sum / N there when any env reset
+     * (extras["episode"]["terrain_level"], the mean of terrain_levels as in legged_gym). */
+    int64_t* terrain_level_sum;
+    float* measured_heights;        /* [N, num_height_x * num_height_y] */
 } lgs_env_buffers;
 
 typedef struct lgs_sim lgs_sim;
@@ -376,7 +421,10 @@ LGS_API int lgs_reset_all(lgs_sim* sim, const lgs_env_buffers* env, int64_t step
 /* reset_idx(env_ids) (legged_robot.py:723-768) for an arbitrary subset: env_mask is a DEVICE
  * byte per env (nonzero = reset).  Resets dofs/root/commands/buffers of those envs, sets their
  * reset byte, and fills the extras like lgs_step (episode means over the reset envs, carried
- * time-outs); the step counter is not advanced. */
+ * time-outs); the step counter is not advanced.  With lgs_task_params.terrain_curriculum the
+ * reset envs first move their terrain level, as in a control step; a mask byte of 2 resets the
+ * env and holds its level (BaseTask.reset: the reset of every env at a runner's construction is
+ * no episode end and must not demote the population; lgs_reset_all moves no level either). */
 LGS_API int lgs_reset_idx(lgs_sim* sim, const lgs_env_buffers* env, const uint8_t* env_mask, int64_t step_counter);
 
 /* lgs_step with its extras left to the step's consumer: the rollout's next policy launch
@@ -460,5 +508,6 @@ LGS_API float lgs_uniform(uint64_t seed, uint32_t env, uint32_t step, uint32_t s
 #define LGS_STREAM_RESET_ROOT 3u
 #define LGS_STREAM_RESET_CMD 4u
 #define LGS_STREAM_PUSH 5u
+#define LGS_STREAM_TERRAIN 6u
 
 #endif /* LEGGEDSIM_H */

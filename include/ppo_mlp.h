@@ -270,6 +270,8 @@ PMLP_API int pmlp_store_step(const float* rewards, const uint8_t* dones, const u
  *   per env i: carry[i] = time_out[i] when any, and the store's bootstrap reads that value;
  *              last_root_vel[i][0:2] = vsim[i] when push and no env was pushed (!pushed[slot]);
  *   once:      ep_means[k] = ep_snapshot[k] = acc[k] / max(acc[nsum], 1) / ep_len_s when any;
+ *              ep_means[nsum] = ep_snapshot[nsum] = *level_sum / num_envs when any and level_sum
+ *              is set (the terrain-level slot after the sums, include/leggedsim.h terrain_level_sum);
  *              acc_next[0..nsum] = 0; pushed[slot ^ 1] = 0; *step_counter += 1.
  * acc is read by every workgroup, so the launch zeroes acc_next (the next step's slot), never acc.
  * acc == NULL: no extras.                                                                     */
@@ -287,6 +289,9 @@ typedef struct {
     uint32_t* pushed;            /* [3] (lgs_get_push_state)                                   */
     int32_t push;                /* push_robots                                                */
     int64_t* step_counter;       /* or NULL                                                    */
+    const int64_t* level_sum;    /* [1] the sum of the envs' terrain levels, or NULL: ep_means and
+                                    ep_snapshot then have no slot [nsum]                        */
+    int32_t num_envs;            /* N (read with level_sum)                                     */
 } pmlp_env_extras;
 /* pmlp_store_step_reset with a deferred step's extras (ex may be NULL) in the same launch; the
  * bootstrap reads the carried time-outs after the launch's own update of them (time_outs is

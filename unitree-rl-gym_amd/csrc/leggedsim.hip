@@ -1926,7 +1926,9 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
         case LGS_REW_FEET_SWING_HEIGHT:
             if (lane < nf) {
                 const int contact = sqrtf(F0 * F0 + F1 * F1 + F2 * F2) > 1.f;
-                const float d = rbs[13 * in.fb + 2] - T.swing_height_target;
+                float fz = rbs[13 * in.fb + 2];
+                if (T.ground_relative_heights) fz = fz - mi[17 + lane];  // (above the ground under the foot)
+                const float d = fz - T.swing_height_target;
                 v = d * d * (contact ? 0.f : 1.f);
             }
             break;
@@ -1973,7 +1975,11 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
         case LGS_REW_LIN_VEL_Z: r = bl[2] * bl[2]; break;
         case LGS_REW_ANG_VEL_XY: r = ba[0] * ba[0] + ba[1] * ba[1]; break;
         case LGS_REW_ORIENTATION: r = pg[0] * pg[0] + pg[1] * pg[1]; break;
-        case LGS_REW_BASE_HEIGHT: { float d = s.root[2] - T.base_height_target; r = d * d; } break;
+        case LGS_REW_BASE_HEIGHT: {
+            float z = s.root[2];
+            if (T.ground_relative_heights) z = mi[16];  // (the mean height above the scanned ground)
+            float d = z - T.base_height_target; r = d * d;
+        } break;
         case LGS_REW_TRACKING_LIN_VEL: {
             float e0 = cmd[0] - bl[0], e1 = cmd[1] - bl[1];
             x = e0 * e0 + e1 * e1; track = true;
@@ -2037,6 +2043,102 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
         if (track) r = lgs_expf(-x / T.tracking_sigma);
     }
     return r;
+}
+
+// ---- rough terrain: the height scan and the ground under the height terms ----
+// What the rough-terrain stages read of the caller's lgs_env_buffers (and the map's horizontal
+// scale), kept in device memory right after the sim's copy of lgs_task_params.  A field of a
+// by-value kernel argument is loaded at kernel entry and holds its SGPRs through the whole
+// physics; k_step's 48-row variants have none to spare (each such field, and each use of the
+// DevSim argument after the physics, grew their scratch), so the post-physics stages read
+// these through the task pointer, at the point of use -- the map included.  The host refreshes
+// the block when a call's values differ from the last ones (sync_terrain_tail).
+struct TerrainTail {
+    long long* levels;         // lgs_env_buffers::terrain_levels
+    const long long* types;    // terrain_types
+    const float* origins;      // terrain_origins
+    long long* level_sum;      // terrain_level_sum
+    float* heights;            // measured_heights
+    float hf_hs;               // horizontal_scale itself: the scan divides by it like legged_gym's _get_heights
+    // DevSim's heightfield (lgs_set_heightfield); hf == nullptr: the z = 0 plane
+    float hf_inv_hs, hf_vs, hf_border;
+    const int16_t* hf;
+    int hf_rows, hf_cols;
+};
+// terrain_sample's height (same arithmetic, no normal) on the block's copy of the map
+__device__ __forceinline__ float tail_ground(const TerrainTail& X, float x, float y) {
+    if (!X.hf) return 0.f;
+    float u = (x + X.hf_border) * X.hf_inv_hs, v = (y + X.hf_border) * X.hf_inv_hs;
+    u = fminf(fmaxf(u, 0.f), (float)(X.hf_rows - 1));
+    v = fminf(fmaxf(v, 0.f), (float)(X.hf_cols - 1));
+    const int i = min((int)u, X.hf_rows - 2), j = min((int)v, X.hf_cols - 2);
+    const float fu = u - (float)i, fv = v - (float)j;
+    const int16_t* h0 = X.hf + (size_t)i * X.hf_cols + j;
+    const float h00 = (float)h0[0] * X.hf_vs, h01 = (float)h0[1] * X.hf_vs;
+    const float h10 = (float)h0[X.hf_cols] * X.hf_vs, h11 = (float)h0[X.hf_cols + 1] * X.hf_vs;
+    float du, dv;
+    if (fu >= fv) { du = h10 - h00; dv = h11 - h10; }
+    else { du = h11 - h01; dv = h01 - h00; }
+    return h00 + fu * du + fv * dv;
+}
+__device__ __forceinline__ const TerrainTail& terrain_tail(const lgs_task_params& T) {
+    return *reinterpret_cast<const TerrainTail*>(&T + 1);
+}
+__global__ void k_set_terrain_tail(TerrainTail* dst, TerrainTail v) { *dst = v; }
+// legged_gym's _get_heights for this env: the grid points of the task rotated by the base yaw
+// (the yaw-only quaternion (0, 0, qz, qw) normalised: no transcendental), moved to the base,
+// truncated to a map cell, the lowest of the cell's three samples.  One point per lane,
+// strided; the int16 map is L2-resident like the contact lanes' reads.  Operation order:
+// include/leggedsim.h (measure_heights).  Every map index is clipped before the read.
+template <int EPW>
+__device__ __forceinline__ void height_scan(const TerrainTail& sp, const lgs_task_params& T, const float* root,
+                                            float* out) {
+    const int lane = hl<EPW>();
+    const int ny = T.num_height_y, P = T.num_height_x * ny;
+    const float qz = root[5], qw = root[6];
+    const float nq = sqrtf(qz * qz + qw * qw);
+    const float z = qz / nq, w = qw / nq;
+    const float c = w * w - z * z, sn = 2.f * w * z;
+    const float bx = root[0], by = root[1];
+    for (int k = lane; k < P; k += WAVE / EPW) {
+        const int ix = k / ny, iy = k - ix * ny;
+        float h = 0.f;
+        if (sp.hf) {
+            const float px = T.height_points_x[ix], py = T.height_points_y[iy];
+            const float X = ((c * px - sn * py) + bx) + sp.hf_border;
+            const float Y = ((sn * px + c * py) + by) + sp.hf_border;
+            const int i = min(max((int)(X / sp.hf_hs), 0), sp.hf_rows - 2);
+            const int j = min(max((int)(Y / sp.hf_hs), 0), sp.hf_cols - 2);
+            const int16_t* h0 = sp.hf + (size_t)i * sp.hf_cols + j;
+            const int hm = min(min((int)h0[0], (int)h0[sp.hf_cols]), (int)h0[1]);
+            h = (float)hm * sp.hf_vs;
+        }
+        out[k] = h;
+    }
+}
+
+// ground_relative_heights: what the base_height and feet_swing_height terms read, into
+// misc[16] (the mean of root_z - measured_heights over the scan) and misc[17 + f] (the ground
+// under foot f: terrain_sample's triangle).  The mean's order is fixed and does not depend on
+// the envs per wave: partial j < 32 adds its points k = j, j + 32, ... in rising k, the
+// partials are added j = 0..31, the total is divided by P.  The heights are read back from
+// the env buffer (after a barrier), so the split step's second launch takes the same path.
+template <int D, int B, int ROWS, int EPW>
+__device__ __forceinline__ void ground_heights(Smem<D, B, ROWS>& s, const lgs_task_params& T, const float* rbs,
+                                               int e, const RewardIn& in) {
+    const int lane = hl<EPW>();
+    const int P = T.num_height_x * T.num_height_y;
+    const TerrainTail& X = terrain_tail(T);
+    const float* mh = X.heights + (size_t)P * e;
+    const float rz = s.root[2];
+    float part = 0.f;
+    if (lane < 32)
+        for (int k = lane; k < P; k += 32) part += rz - mh[k];
+    float tot = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) tot += bc<EPW>(part, j);
+    if (lane == 0) s.u.post.misc[16] = tot / (float)P;
+    if (rbs && lane < T.num_feet) s.u.post.misc[17 + lane] = tail_ground(X, rbs[13 * in.fb], rbs[13 * in.fb + 1]);
 }
 
 // post_physics parts: everything, only up to the rewards (lgs_post_physics_rewards), or
@@ -2160,10 +2262,17 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
         const int timeout = (float)ep > T.max_episode_length;
         const int reset = (hballot<EPW>(term) != 0ull) | timeout;
         if (lane == 0) { s.flags[0] = reset; s.flags[1] = timeout; }
+        // the height scan, where legged_gym's callback measures (post-physics, pre-reset state)
+        if (T.measure_heights) {
+            const TerrainTail& X = terrain_tail(T);
+            height_scan<EPW>(X, T, s.root, X.heights + (size_t)(T.num_height_x * T.num_height_y) * e);
+        }
     }
     if (part == PART_PREPARE) return;  // (the base-frame state and commands are in E)
     __syncthreads();
     STAMP(24);
+    if (T.ground_relative_heights)
+        ground_heights<D, B, ROWS, EPW>(s, T, rbs, e, in);  // (reward_terms' barrier orders misc)
     // rewards: lane k holds active term k (alphabetical order, legged_robot.py:770-787)
     float r = reward_terms<D, B, ROWS, EPW, PAD>(s, T, E, rbs, e, in);
     if (lane < T.num_rewards) {
@@ -2202,7 +2311,9 @@ __device__ __forceinline__ int num_sums(const lgs_task_params& T) {
 // reset modes of post_physics: the control step (reset decided by check_termination),
 // BaseTask.reset (every env, no episode extras), reset_idx(env_ids) (the masked envs:
 // episode sums into the extras accumulator, reset_buf set, legged_robot.py:723-768)
-enum { RESET_STEP = 0, RESET_ALL = 1, RESET_IDS = 2 };
+// RESET_IDS_HOLD: reset_idx(env_ids) that leaves the terrain levels alone (mask byte 2:
+// BaseTask.reset, the whole-population reset at a runner's construction, is no episode end)
+enum { RESET_STEP = 0, RESET_ALL = 1, RESET_IDS = 2, RESET_IDS_HOLD = 3 };
 
 template <int D, int B, int ROWS, int EPW, bool PAD = false>
 __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, const lgs_env_buffers& E,
@@ -2244,10 +2355,46 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         if (lane < A) { act[lane] = 0.f; E.actions[A * e + lane] = 0.f; E.last_actions[A * e + lane] = 0.f; }
         if (lane < T.num_feet) E.feet_air_time[T.num_feet * e + lane] = 0.f;
         float rv = (lane < 6) ? rand_range(-0.5f, 0.5f, philox_uniform(seed, e, step, LGS_STREAM_RESET_ROOT, lane)) : 0.f;
+        // lanes 0-2: the env origin's component.  The level curriculum (the rule and its
+        // operation order: include/leggedsim.h, terrain_curriculum) moves it first, on the pre-reset
+        // root xy and commands; BaseTask.reset moves no level.  Each of the three lanes evaluates the
+        // rule (same inputs, same level) and takes its component; lane 0 records the level.
+        float org = 0.f;
+        if (lane < 3) {
+            org = E.env_origins[3 * e + lane];
+            if (T.terrain_curriculum && (reset_mode == RESET_STEP || reset_mode == RESET_IDS)) {
+                const TerrainTail& X = terrain_tail(T);
+                const float dx = s.root[0] - E.env_origins[3 * e], dy = s.root[1] - E.env_origins[3 * e + 1];
+                const float d2 = dx * dx + dy * dy;
+                // (lgs_reset_idx runs no callback: the commands are the env buffer's)
+                const float cx = reset_mode == RESET_IDS ? E.commands[4 * e] : s.u.post.misc[12];
+                const float cy = reset_mode == RESET_IDS ? E.commands[4 * e + 1] : s.u.post.misc[13];
+                const float half = 0.5f * T.max_episode_length_s;
+                const bool up = d2 > T.terrain_half_length_sq;
+                const bool down = !up && d2 < (cx * cx + cy * cy) * (half * half);
+                const long long L0 = X.levels[e];
+                const int rows = T.terrain_rows, cols = T.terrain_cols;
+                long long Ln = L0 + (up ? 1 : 0) - (down ? 1 : 0);
+                int L;
+                if (Ln >= rows)  // past the top row: a random level (legged_gym's graduation)
+                    L = min((int)(philox_uniform(seed, e, step, LGS_STREAM_TERRAIN, 0) * (float)rows), rows - 1);
+                else
+                    L = Ln > 0 ? (int)Ln : 0;
+                const long long ty = X.types[e];
+                const int type = ty < 0 ? 0 : (ty >= cols ? cols - 1 : (int)ty);  // (a tile of the table)
+                org = X.origins[3 * ((size_t)L * cols + type) + lane];
+                E.env_origins[3 * e + lane] = org;
+                if (lane == 0) {
+                    X.levels[e] = L;
+                    if (X.level_sum && (long long)L != L0)
+                        atomicAdd((unsigned long long*)X.level_sum, (unsigned long long)((long long)L - L0));
+                }
+            }
+        }
         __syncthreads();
         if (lane < 13) {
             float x = T.base_init_state[lane];
-            if (lane < 3) x += E.env_origins[3 * e + lane];
+            if (lane < 3) x += org;
             // terrain origins: xy within 1 m of the tile centre (legged_robot.py:582-585)
             if (lane < 2 && T.custom_origins)
                 x += rand_range(-1.f, 1.f, philox_uniform(seed, e, step, LGS_STREAM_RESET_ROOT, 6 + lane));
@@ -2255,7 +2402,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         }
         __syncthreads();
         if (lane < 6) s.root[7 + lane] = rv;
-        if (reset_mode == RESET_IDS && lane == 0) E.reset[e] = 1;  // reset_buf[env_ids] = 1 (:758)
+        if (reset_mode >= RESET_IDS && lane == 0) E.reset[e] = 1;  // reset_buf[env_ids] = 1 (:758)
         if (reset_mode != RESET_ALL) {
             // (strided: two envs per wave leave 32 lanes per env, and a task may have more sums)
             const int nsum = num_sums(T);
@@ -2499,7 +2646,8 @@ __global__ __launch_bounds__(WAVE) void k_reset_all(DevModel md, DevState st, co
     if (threadIdx.x < 3 * B)
         (&s.cf[0][0])[threadIdx.x] = threadIdx.x < 3 * Br ? st.cforce[(size_t)3 * Br * e + threadIdx.x] : 0.f;
     __syncthreads();
-    post_physics<D, B, ROWS, 1, PAD>(s, *Tp, E, nullptr, N, e, step, mask ? RESET_IDS : RESET_ALL);
+    post_physics<D, B, ROWS, 1, PAD>(s, *Tp, E, nullptr, N, e, step,
+                                     mask ? (mask[e] == 2 ? RESET_IDS_HOLD : RESET_IDS) : RESET_ALL);
     __syncthreads();
     store_state<D, B, ROWS, 1, PAD>(s, st, md, e);
     if (st.rbs) body_states<D, B, ROWS, 1>(s, mc, st.rbs + (size_t)13 * Br * e, Br);
@@ -2543,6 +2691,14 @@ __global__ __launch_bounds__(1024) void k_step_extras(lgs_env_buffers E, const l
         E.ep_means[t] = m;
         if (E.ep_snapshot) E.ep_snapshot[t] = m;
     }
+    // extras["episode"]["terrain_level"]: the mean level of ALL envs, from the exact integer sum
+    // the reset envs keep (order-free), in the slot after the episode sums
+    if (E.terrain_level_sum && E.ep_means && t == nsum) {
+        float m = E.ep_means[nsum];
+        if (any) m = (float)*E.terrain_level_sum / (float)N;
+        E.ep_means[nsum] = m;
+        if (E.ep_snapshot) E.ep_snapshot[nsum] = m;
+    }
     if (E.time_outs_carry && any)
         for (int e = t; e < N; e += blockDim.x) E.time_outs_carry[e] = E.time_out[e];
     __syncthreads();
@@ -2583,6 +2739,9 @@ struct lgs_sim {
     int16_t* hf_mem = nullptr;
     float4* self_mem = nullptr;
     int has_task = 0;
+    int task_curriculum = 0, task_heights = 0;  // the task's rough-terrain switches (env buffers checked per call)
+    float hf_hs = 0.f;           // the heightfield's horizontal scale (TerrainTail::hf_hs)
+    TerrainTail tail_host{};     // what the device block after task_dev holds (sync_terrain_tail)
     int rows = 32;
     int chain = 0;  // dof_chain_length of the model
     int epw = 1;    // envs per wave of k_step (2 for the 32-row variant at even N)
@@ -2971,7 +3130,9 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
         HIP_TRY(hipMemcpy(s->friction, ones, sizeof(float) * num_envs, hipMemcpyHostToDevice));
         free(ones);
     }
-    HIP_TRY(hipMalloc(&s->task_dev, sizeof(lgs_task_params)));
+    static_assert(sizeof(lgs_task_params) % alignof(TerrainTail) == 0, "TerrainTail follows lgs_task_params");
+    HIP_TRY(hipMalloc(&s->task_dev, sizeof(lgs_task_params) + sizeof(TerrainTail)));
+    HIP_TRY(hipMemset(s->task_dev, 0, sizeof(lgs_task_params) + sizeof(TerrainTail)));
     *out = s;
     return LGS_OK;
 }
@@ -3008,6 +3169,7 @@ LGS_API int lgs_set_heightfield(lgs_sim* s, const int16_t* heights, int32_t rows
     s->sp.hf = s->hf_mem;
     s->sp.hf_rows = rows; s->sp.hf_cols = cols;
     s->sp.hf_inv_hs = 1.0f / horizontal_scale;
+    s->hf_hs = horizontal_scale;
     s->sp.hf_vs = vertical_scale;
     s->sp.hf_border = border_size;
     // slope bound of the map for the contact pre-filter: the largest gradient norm over the
@@ -3170,6 +3332,13 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
         return set_err(LGS_ERR_ARG, "lgs_set_task: num_front_feet out of range");
     if (t->termination_mode != 0 && t->termination_mode != 1)
         return set_err(LGS_ERR_ARG, "lgs_set_task: unknown termination_mode");
+    if (t->terrain_curriculum && (t->terrain_rows < 1 || t->terrain_cols < 1))
+        return set_err(LGS_ERR_ARG, "lgs_set_task: terrain_curriculum needs terrain_rows, terrain_cols >= 1");
+    if (t->num_height_x < 0 || t->num_height_x > LGS_MAX_HEIGHT_POINTS || t->num_height_y < 0 ||
+        t->num_height_y > LGS_MAX_HEIGHT_POINTS || (t->measure_heights && (t->num_height_x < 1 || t->num_height_y < 1)))
+        return set_err(LGS_ERR_ARG, "lgs_set_task: measure_heights needs 1 <= num_height_x, num_height_y <= 32");
+    if (t->ground_relative_heights && !t->measure_heights)
+        return set_err(LGS_ERR_ARG, "lgs_set_task: ground_relative_heights needs measure_heights");
     if (t->obs_layout == LGS_OBS_HANDSTAND && t->num_obs != 6 + 3 * t->num_actions + t->num_feet)
         return set_err(LGS_ERR_ARG, "lgs_set_task: the handstand layout has 6 + 3 A + num_feet observations");
     lgs_task_params tt = *t;  // a padded model's inert DOFs: no gains, no torque, no limits
@@ -3179,13 +3348,48 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     }
     HIP_TRY(hipMemcpy(s->task_dev, &tt, sizeof(lgs_task_params), hipMemcpyHostToDevice));
     s->has_task = 1;
+    s->task_curriculum = t->terrain_curriculum != 0;
+    s->task_heights = t->measure_heights != 0;
     return LGS_OK;
+}
+
+// the device block the rough-terrain stages read (TerrainTail): refreshed by a one-thread launch
+// on the sim's stream (capturable, ordered before the step) when this call's values are new
+static int sync_terrain_tail(lgs_sim* s, const lgs_env_buffers* env) {
+    if (!s->task_curriculum && !s->task_heights) return LGS_OK;
+    TerrainTail v{};
+    v.levels = (long long*)env->terrain_levels; v.types = (const long long*)env->terrain_types;
+    v.origins = env->terrain_origins; v.level_sum = (long long*)env->terrain_level_sum;
+    v.heights = env->measured_heights; v.hf_hs = s->hf_hs;
+    v.hf = s->sp.hf; v.hf_rows = s->sp.hf_rows; v.hf_cols = s->sp.hf_cols;
+    v.hf_inv_hs = s->sp.hf_inv_hs; v.hf_vs = s->sp.hf_vs; v.hf_border = s->sp.hf_border;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s->stream, &cap);
+    // (inside a capture the launch is always recorded: a replay must not depend on what an
+    // eager call happened to leave)
+    if (cap == hipStreamCaptureStatusNone && memcmp(&v, &s->tail_host, sizeof(v)) == 0) return LGS_OK;
+    hipLaunchKernelGGL(k_set_terrain_tail, dim3(1), dim3(1), 0, s->stream,
+                       reinterpret_cast<TerrainTail*>(s->task_dev + 1), v);
+    HIP_TRY(hipGetLastError());
+    if (cap == hipStreamCaptureStatusNone) s->tail_host = v;  // (a recorded launch has written nothing yet)
+    return LGS_OK;
+}
+
+// the env buffers a rough-terrain switch of the task needs (a missing one is an error, not a
+// skip), then into the device block the step reads them from
+static int check_terrain_buffers(lgs_sim* s, const lgs_env_buffers* env, const char* what) {
+    if (s->task_curriculum && (!env->terrain_levels || !env->terrain_types || !env->terrain_origins))
+        return set_err(LGS_ERR_ARG, std::string(what) + ": terrain_curriculum needs terrain_levels, terrain_types, terrain_origins");
+    if (s->task_heights && !env->measured_heights)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": measure_heights needs the measured_heights buffer");
+    return sync_terrain_tail(s, env);
 }
 
 static int launch_step(lgs_sim* s, const lgs_env_buffers* env, int64_t step_counter, int mode, const char* what,
                        bool extras = true) {
     if (!s || !env) return set_err(LGS_ERR_ARG, std::string(what) + ": null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, std::string(what) + ": state not bound or task not set");
+    if (const int rc = check_terrain_buffers(s, env, what)) return rc;
     DevState st = state_of(s);
     if (pick(s) == V_EXTRA) {
         const int rc = extra_step(s, s->md, s->sp, st, s->task_dev, *env, s->N, (uint32_t)step_counter, mode);
@@ -3267,6 +3471,7 @@ LGS_API int lgs_reset_all(lgs_sim* s, const lgs_env_buffers* env, int64_t step_c
 LGS_API int lgs_reset_idx(lgs_sim* s, const lgs_env_buffers* env, const uint8_t* env_mask, int64_t step_counter) {
     if (!s || !env || !env_mask) return set_err(LGS_ERR_ARG, "lgs_reset_idx: null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_idx: state not bound or task not set");
+    if (const int rc = check_terrain_buffers(s, env, "lgs_reset_idx")) return rc;
     DevState st = state_of(s);
     if (pick(s) == V_EXTRA) {
         const int rc = extra_reset(s, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, env_mask);

@@ -2004,6 +2004,14 @@ __device__ __forceinline__ void ex_once(const pmlp_env_extras& x, bool any, int 
         x.ep_means[t] = m;
         if (x.ep_snapshot) x.ep_snapshot[t] = m;
     }
+    // extras["episode"]["terrain_level"] (k_step_extras' slot after the sums): the mean level of
+    // all envs from the exact integer sum the env step keeps
+    if (x.level_sum && x.ep_means && t == x.nsum) {
+        float m = x.ep_means[x.nsum];
+        if (any) m = (float)*x.level_sum / (float)x.num_envs;
+        x.ep_means[x.nsum] = m;
+        if (x.ep_snapshot) x.ep_snapshot[x.nsum] = m;
+    }
     if (t <= x.nsum) x.acc_next[t] = 0.f;
     if (t == 0) {
         x.pushed[(x.pushed[2] + 1u) & 1u] = 0u;
@@ -2987,7 +2995,7 @@ PMLP_API int pmlp_mlp_forward(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32
 // a deferred env step's extras are complete (acc == NULL: none)
 static bool env_extras_ok(const pmlp_env_extras& x) {
     return !x.acc || (x.acc_next && x.nsum >= 0 && x.nsum < 64 && x.ep_len_s > 0.f && x.time_out && x.pushed &&
-                      (!x.push || !x.last_root_vel || x.vsim));
+                      (!x.push || !x.last_root_vel || x.vsim) && (!x.level_sum || x.num_envs > 0));
 }
 
 PMLP_API int pmlp_rollout_forward(const pmlp_mlp_fwd_job* jobs, int32_t N, const pmlp_rollout_step* r, void* stream) {

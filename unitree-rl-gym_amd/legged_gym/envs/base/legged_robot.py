@@ -30,7 +30,7 @@ from legged_gym.utils.helpers import class_to_dict
 from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
-from leggedsim.task import build_task_params
+from leggedsim.task import build_task_params, terrain_switches
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -94,7 +94,8 @@ class _DeferredExtras:
                            nsum=tp.num_rewards + (1 if tp.has_termination_reward else 0) + tp.num_extra_sums,
                            ep_len_s=float(tp.max_episode_length_s), ep_means=E.ep_means, ep_snapshot=E.ep_snapshot,
                            time_out=E.time_out, carry=E.time_outs_carry, last_root_vel=E.last_root_vel, vsim=vsim,
-                           pushed=pushed, push=int(bool(tp.push_robots)), step_counter=E.step_counter)
+                           pushed=pushed, push=int(bool(tp.push_robots)), step_counter=E.step_counter,
+                           level_sum=E.terrain_level_sum, num_envs=env.num_envs)
         self.consumed = False
 
     def run(self):
@@ -120,6 +121,7 @@ class LeggedRobot(BaseTask):
     max_contacts = 8
     max_rows = 32
     max_self_contacts = 4  # contact slots self contacts may take per substep (cfg.asset.self_collisions == 0)
+    _hold_terrain_levels = False  # True inside reset(): its reset_idx moves no terrain level
     # The reference's per-step methods a task may override in Python, as its H1Robot / G1Robot
     # do (h1_env.py:55-95, g1_env.py:56-141): the step then takes its split path and calls the
     # override at the reference's point of post_physics_step (:692, :695, :704), between native
@@ -200,6 +202,9 @@ class LeggedRobot(BaseTask):
         self.max_episode_length_s = self.cfg.env.episode_length_s
         self.max_episode_length = np.ceil(self.max_episode_length_s / self.dt)
         self.cfg.domain_rand.push_interval = np.ceil(self.cfg.domain_rand.push_interval_s / self.dt)
+        # the rough-terrain switches; refused on a plane, and the ground-relative
+        # height terms without the scan
+        self.level_curriculum, self.scan_heights, self.ground_relative_heights = terrain_switches(self.cfg)
 
     # ------------------------------------------------------------- sim ------
     def create_sim(self):
@@ -378,6 +383,17 @@ class LeggedRobot(BaseTask):
         self.time_out_buf = self._timeout_bufs[0]
         self.rew_buf = torch.zeros(N, dtype=torch.float, device=dev)
         self.noise_scale_vec = self._get_noise_scale_vec(self.cfg)
+        # the height scan (legged_gym's measured_heights, point k = ix * len(y) + iy), refreshed by
+        # every control step from the post-physics, pre-reset state; a compute_observations hook
+        # may read it
+        if self.scan_heights:
+            tc = self.cfg.terrain
+            self.num_height_points = len(tc.measured_points_x) * len(tc.measured_points_y)
+            self.measured_heights = torch.zeros(N, self.num_height_points, dtype=torch.float, device=dev)
+        # the exact sum of terrain_levels the level curriculum keeps for extras["episode"]["terrain_level"]
+        self._terrain_level_sum = None
+        if self.level_curriculum:
+            self._terrain_level_sum = self.terrain_levels.sum().to(torch.int64).reshape(())
 
         # default joint angles and PD gains by name substring, last match wins (:168-186)
         self.default_dof_pos = torch.tensor(self.spec.default_dof_pos, device=dev)
@@ -444,7 +460,10 @@ class LeggedRobot(BaseTask):
         # two accumulator slots, one per env-buffer parity: a deferred step's consumer zeroes the
         # next step's slot while its workgroups still read this step's (lgs_step_deferred)
         self._episode_acc = torch.zeros(2, nsum + 1, dtype=torch.float, device=self.device)
-        self._ep_means = torch.zeros(nsum, dtype=torch.float, device=self.device)
+        # (the level curriculum's slot after the sums: the mean terrain level, seeded here)
+        self._ep_means = torch.zeros(nsum + int(self.level_curriculum), dtype=torch.float, device=self.device)
+        if self.level_curriculum:
+            self._ep_means[nsum] = self.terrain_levels.float().mean()
         self._time_outs = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
 
     # ------------------------------------------------------ native task -----
@@ -490,7 +509,32 @@ class LeggedRobot(BaseTask):
         E.ep_means = p(self._ep_means)
         E.ep_snapshot = None  # set per step (step())
         E.time_outs_carry = p(self._time_outs) if self.cfg.env.send_timeouts else None
+        if self.level_curriculum:
+            E.terrain_levels = p(self.terrain_levels)
+            E.terrain_types = p(self.terrain_types)
+            E.terrain_origins = p(self.terrain_origins)
+            E.terrain_level_sum = p(self._terrain_level_sum)
+        if self.scan_heights:
+            E.measured_heights = p(self.measured_heights)
         return E
+
+    def set_terrain_levels(self, levels):
+        """Put the envs on the terrain rows `levels` [N]: terrain_levels, env_origins and the level
+        sum behind extras["episode"]["terrain_level"] stay consistent (the robots move at their
+        next reset).  Writing terrain_levels directly leaves the other two stale."""
+        self.terrain_levels.copy_(torch.as_tensor(levels, device=self.device).long().clamp(0, self.max_terrain_level - 1))
+        self.env_origins[:] = self.terrain_origins[self.terrain_levels, self.terrain_types]
+        if self._terrain_level_sum is not None:
+            self._terrain_level_sum.copy_(self.terrain_levels.sum())
+            self._ep_means[len(self._sum_names)] = self.terrain_levels.float().mean()
+
+    def _episode_extras(self, snap):
+        """extras["episode"] of the snapshot a step (or reset_idx) filled: rew_<term> per episode
+        sum, and with the level curriculum terrain_level, the mean of terrain_levels over all envs."""
+        ep = {"rew_" + k: snap[j] for j, k in enumerate(self._sum_names)}
+        if self.level_curriculum:
+            ep["terrain_level"] = snap[len(self._sum_names)]
+        return ep
 
     @property
     def common_step_counter(self):
@@ -542,7 +586,7 @@ class LeggedRobot(BaseTask):
             E.actions_in = None
         # this step's extras["episode"] values (a fresh buffer per step, like the
         # reference's per-reset tensors; inside a captured rollout, one per step)
-        snap = torch.empty(len(self._sum_names), dtype=torch.float, device=self.device)
+        snap = torch.empty(self._ep_means.numel(), dtype=torch.float, device=self.device)
         E.ep_snapshot = snap.data_ptr()
         job = None
         if self._split_step:
@@ -561,7 +605,7 @@ class LeggedRobot(BaseTask):
         self.privileged_obs_buf = self._priv_bufs[i]
         self.reset_buf = self._reset_bufs[i]
         self.time_out_buf = self._timeout_bufs[i]
-        self.extras["episode"] = {"rew_" + k: snap[j] for j, k in enumerate(self._sum_names)}
+        self.extras["episode"] = self._episode_extras(snap)
         if self.cfg.env.send_timeouts:
             self.extras["time_outs"] = self._time_outs
         if job is not None:
@@ -663,21 +707,33 @@ class LeggedRobot(BaseTask):
         """reset_idx (legged_robot.py:723-768) for any subset of envs: one masked launch
         (lgs_reset_idx) resets dofs, root states and commands, zeroes the actions and
         buffers, sets reset_buf[env_ids] = 1 and fills extras["episode"] (means of the
-        reset envs' episode sums / episode_length_s) and extras["time_outs"]."""
+        reset envs' episode sums / episode_length_s) and extras["time_outs"].  With
+        cfg.terrain.level_curriculum the envs first move their terrain level, as in a control
+        step; BaseTask.reset() (every env, at a runner's construction) moves none."""
         if len(env_ids) == 0:
             return
         self._sync_stream()
         self.flush_extras()
         ids = torch.as_tensor(env_ids, device=self.device).long().view(-1)
         mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
-        mask[ids] = 1
+        mask[ids] = 2 if (self.level_curriculum and self._hold_terrain_levels) else 1  # (2: reset, level held)
         E = self._env_structs[self._buf_idx]
-        snap = torch.empty(len(self._sum_names), dtype=torch.float, device=self.device)
+        snap = torch.empty(self._ep_means.numel(), dtype=torch.float, device=self.device)
         E.ep_snapshot = snap.data_ptr()
         self.sim.reset_idx(E, mask, self.common_step_counter)
-        self.extras["episode"] = {"rew_" + k: snap[i] for i, k in enumerate(self._sum_names)}
+        self.extras["episode"] = self._episode_extras(snap)
         if self.cfg.env.send_timeouts:
             self.extras["time_outs"] = self._time_outs
+
+    def reset(self):
+        """BaseTask.reset (base_task.py:82-86): reset_idx of every env, then a zero-action step.
+        This reset_idx moves no terrain level: a runner calls reset() at construction, every
+        robot then stands at its tile centre, and the rule would demote the whole population."""
+        self._hold_terrain_levels = True
+        try:
+            return super().reset()
+        finally:
+            self._hold_terrain_levels = False
 
     def post_physics_step(self):
         raise RuntimeError("post_physics_step runs inside the fused native step()")

@@ -35,6 +35,12 @@ class LeggedRobotCfg(BaseConfig):
         num_cols = 20
         terrain_proportions = [0.1, 0.1, 0.35, 0.25, 0.2]
         slope_treshold = 0.75
+        # rough-terrain switches of the fused step, off by default; none works on a plane
+        # level_curriculum: a resetting env moves up / down a tile row (legged_gym's
+        # _update_terrain_curriculum).  `curriculum` above only lays the map out in difficulty rows.
+        level_curriculum = False
+        # scan_heights: env.measured_heights [N, len(x) * len(y)] of measured_points_x / _y every step
+        scan_heights = False
 
     class commands:
         curriculum = False
@@ -118,6 +124,9 @@ class LeggedRobotCfg(BaseConfig):
         soft_torque_limit = 1.0
         base_height_target = 1.0
         max_contact_force = 100.0
+        # base_height and feet_swing_height measure from the ground under the robot, not from
+        # world z = 0 (needs terrain.scan_heights)
+        ground_relative_heights = False
 
     class normalization:
         class obs_scales:

@@ -95,3 +95,16 @@ class G1HeightfieldCfg(G1RoughCfg):
 
     class terrain(G1RoughCfg.terrain):
         mesh_type = "heightfield"
+
+
+class G1TerrainCfg(G1HeightfieldCfg):
+    """g1_terrain: G1HeightfieldCfg with the rough-terrain path of the fused step on:
+    the level curriculum at reset, the height scan, and base_height / feet_swing_height measured
+    from the ground instead of world z."""
+
+    class terrain(G1HeightfieldCfg.terrain):
+        level_curriculum = True
+        scan_heights = True
+
+    class rewards(G1HeightfieldCfg.rewards):
+        ground_relative_heights = True

@@ -50,6 +50,8 @@ def reward_id(name, task_aliases=None):
     return REWARD_ID.get(REWARD_ALIASES.get(name, name))
 
 STREAM_NOISE, STREAM_CMD, STREAM_RESET_DOF, STREAM_RESET_ROOT, STREAM_RESET_CMD, STREAM_PUSH = range(6)
+STREAM_TERRAIN = 6  # the level curriculum's graduation draw
+MAX_HEIGHT_POINTS = 32
 
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
@@ -138,6 +140,12 @@ class TaskParams(C.Structure):
         ("num_front_feet", C.c_int32),
         ("contact_flag_threshold", C.c_float), ("contact_flip_prob", C.c_float),
         ("feet_together_target", C.c_float),
+        # rough-terrain switches (all 0: off)
+        ("terrain_curriculum", C.c_int32), ("terrain_rows", C.c_int32), ("terrain_cols", C.c_int32),
+        ("terrain_half_length_sq", C.c_float),
+        ("measure_heights", C.c_int32), ("num_height_x", C.c_int32), ("num_height_y", C.c_int32),
+        ("height_points_x", C.c_float * MAX_HEIGHT_POINTS), ("height_points_y", C.c_float * MAX_HEIGHT_POINTS),
+        ("ground_relative_heights", C.c_int32),
     ]
 
 
@@ -147,7 +155,8 @@ class EnvBuffers(C.Structure):
         "last_contacts", "episode_length", "obs", "priv_obs", "rew", "reset", "time_out", "episode_sums",
         "episode_acc", "base_lin_vel", "base_ang_vel", "projected_gravity", "rpy", "env_origins", "phase",
         "leg_phase", "rew_terms", "step_counter", "ep_means", "ep_snapshot", "time_outs_carry", "actions_in",
-        "episode_acc_next")]
+        "episode_acc_next", "terrain_levels", "terrain_types", "terrain_origins", "terrain_level_sum",
+        "measured_heights")]
 
 
 class ModelHandle:

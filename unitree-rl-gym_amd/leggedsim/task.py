@@ -125,7 +125,48 @@ def build_task_params(env) -> cabi.TaskParams:
         T.body_state_mask = sum(1 << b for b in fi) if fi else 0
     T.custom_origins = int(bool(getattr(env, "custom_origins", False)))
     _native_task_switches(T, env, A)
+    _terrain_switches(T, env)
     return T
+
+
+def terrain_switches(cfg):
+    """(level_curriculum, scan_heights, ground_relative_heights) of a cfg, refusing the combinations
+    the step cannot honour: any of them on a plane (there is no map to move on or to scan), and
+    ground-relative height terms without the scan they average."""
+    tc, rw = cfg.terrain, cfg.rewards
+    cur = bool(getattr(tc, "level_curriculum", False))
+    scan = bool(getattr(tc, "scan_heights", False))
+    rel = bool(getattr(rw, "ground_relative_heights", False))
+    if tc.mesh_type not in ("heightfield", "trimesh"):
+        on = [n for n, v in (("terrain.level_curriculum", cur), ("terrain.scan_heights", scan),
+                             ("rewards.ground_relative_heights", rel)) if v]
+        if on:
+            raise ValueError(f"{', '.join(on)} need a terrain map (terrain.mesh_type 'heightfield' or 'trimesh'), "
+                             f"not {tc.mesh_type!r}")
+    if rel and not scan:
+        raise ValueError("rewards.ground_relative_heights needs terrain.scan_heights (base_height averages the scan)")
+    return cur, scan, rel
+
+
+def _terrain_switches(T, env):
+    """The rough-terrain switches: the level curriculum's tile table and threshold, the
+    height scan's grid, the ground-relative height terms."""
+    cfg = env.cfg
+    cur, scan, rel = terrain_switches(cfg)
+    tc = cfg.terrain
+    if cur:
+        T.terrain_curriculum = 1
+        T.terrain_rows, T.terrain_cols = int(tc.num_rows), int(tc.num_cols)
+        T.terrain_half_length_sq = float(np.float32(0.5 * tc.terrain_length) ** 2)
+    if scan:
+        px, py = list(tc.measured_points_x), list(tc.measured_points_y)
+        if not (1 <= len(px) <= cabi.MAX_HEIGHT_POINTS and 1 <= len(py) <= cabi.MAX_HEIGHT_POINTS):
+            raise ValueError(f"terrain.measured_points_x / _y: 1 to {cabi.MAX_HEIGHT_POINTS} entries each")
+        T.measure_heights = 1
+        T.num_height_x, T.num_height_y = len(px), len(py)
+        _put(T.height_points_x, px)
+        _put(T.height_points_y, py)
+    T.ground_relative_heights = int(rel)
 
 
 def _native_task_switches(T, env, A):

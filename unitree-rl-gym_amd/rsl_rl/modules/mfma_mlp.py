@@ -81,7 +81,7 @@ class EnvExtras(C.Structure):
     _fields_ = [("acc", C.c_void_p), ("acc_next", C.c_void_p), ("nsum", C.c_int32), ("ep_len_s", C.c_float)] + \
         [(n, C.c_void_p) for n in ("ep_means", "ep_snapshot", "time_out", "carry", "last_root_vel", "vsim",
                                    "pushed")] + \
-        [("push", C.c_int32), ("step_counter", C.c_void_p)]
+        [("push", C.c_int32), ("step_counter", C.c_void_p), ("level_sum", C.c_void_p), ("num_envs", C.c_int32)]
 
 
 class RolloutStep(C.Structure):
