@@ -293,6 +293,30 @@ typedef struct lgs_task_params {
 } lgs_task_params;
 #define LGS_MAX_HEIGHT_POINTS 32
 
+/* ---- the height scan in the observation row (lgs_set_height_observations) ----
+ * enabled = 1 appends legged_gym's compute_observations tail to every observation row: with
+ * P = num_height_x * num_height_y and `head` the layout's own width (LGS_OBS_QUADRUPED 12 + 3 A;
+ * LGS_OBS_HUMANOID 11 + 3 A, privileged 14 + 3 A), the task's num_obs is head + P (and
+ * num_privileged_obs, when the humanoid layout has that row, its head + P), and entry head + k is
+ *   h    = clip((root_z - offset) - measured_heights[e][k], -clip, clip) * scale
+ *   obs  = clip(h + (2u - 1) * noise_scale, -clip_observations, clip_observations)
+ *   priv = clip(h, -clip_observations, clip_observations)            (humanoid layout only)
+ * in fp32 without contraction; the noise only with add_noise, u = LGS_STREAM_NOISE draw head + k
+ * (the head keeps its draws 0 .. head - 1, its arithmetic and its bits).  root_z is the root after
+ * the step's reset; measured_heights is what the step measured before the reset (legged_gym's own
+ * order: a reset env observes one row of heights from where its last episode ended).
+ * Needs measure_heights and a layout other than LGS_OBS_HANDSTAND; head <= LGS_MAX_OBS and
+ * P <= LGS_MAX_SCAN_OBS.  This call and lgs_set_task may come in either order: the pair is checked
+ * by every step / reset entry point, which refuses an inconsistent one before any launch. */
+#define LGS_MAX_SCAN_OBS 256
+typedef struct lgs_height_obs {
+    int32_t enabled;
+    float offset;        /* legged_gym: 0.5 */
+    float clip;          /* legged_gym: 1.0 */
+    float scale;         /* normalization.obs_scales.height_measurements */
+    float noise_scale;   /* noise_scales.height_measurements * noise_level * scale */
+} lgs_height_obs;
+
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */
 typedef struct lgs_env_buffers {
     float* actions;          /* [N,A] in: raw policy actions; out: clipped env.actions (0 on reset) */
@@ -451,6 +475,10 @@ LGS_API int lgs_get_push_state(lgs_sim* sim, float** vsim, uint32_t** pushed);
  * Replaces the z = 0 plane for every env; heights = NULL (or rows = 0) restores the plane. */
 LGS_API int lgs_set_heightfield(lgs_sim* sim, const int16_t* heights, int32_t rows, int32_t cols,
                                 float horizontal_scale, float vertical_scale, float border_size);
+
+/* the height scan as the tail of the observation rows (lgs_height_obs above); desc = NULL or
+ * enabled = 0: the rows are the layout's own (the default) */
+LGS_API int lgs_set_height_observations(lgs_sim* sim, const lgs_height_obs* desc);
 
 /* create_actor(..., self_collisions, 0) (legged_robot.py:373-374): the self-collision
  * proxies and pairs of every env (host descriptor, copied; NULL or num_pairs = 0: off) */

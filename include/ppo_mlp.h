@@ -322,7 +322,7 @@ PMLP_API int pmlp_permutation(int64_t* out, int64_t n, uint64_t seed, void* stre
  * chip (LDS) between layers.  Optional stores: xa = the bf16 input rows [M, K0] and y[l] = the
  * bf16 hidden outputs (the backward's operands).  Bitwise equal to the per-layer pmlp_gemm
  * forward (FWD_HIDDEN x3 with the af operand form, FWD_OUT).  Limits: K0 a multiple of 16,
- * <= 64; N0, N2 <= 512 and N1 <= 256, multiples of 32; N3 <= 32; 1..2 jobs.              */
+ * <= 256; N0, N2 <= 512 and N1 <= 256, multiples of 32; N3 <= 32; 1..2 jobs.              */
 typedef struct {
     const float* x;
     const int64_t* rows;

@@ -2064,6 +2064,10 @@ struct TerrainTail {
     float hf_inv_hs, hf_vs, hf_border;
     const int16_t* hf;
     int hf_rows, hf_cols;
+    // lgs_set_height_observations: obs_scan = the scan's points when they are the
+    // tail of the observation rows, else 0
+    int obs_scan;
+    float obs_offset, obs_clip, obs_scale, obs_noise;
 };
 // terrain_sample's height (same arithmetic, no normal) on the block's copy of the map
 __device__ __forceinline__ float tail_ground(const TerrainTail& X, float x, float y) {
@@ -2471,7 +2475,10 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
     STAMP(28);
     const int O = T.num_obs, P = T.num_privileged_obs;
     const int off = (T.obs_layout == LGS_OBS_HUMANOID) ? 3 : 0;
-    for (int i = lane; i < O; i += WAVE / EPW) {
+    // S > 0: the last S entries of the rows are the height scan (below); the head keeps its
+    // indices, its draws and its arithmetic
+    const int S = T.measure_heights ? terrain_tail(T).obs_scan : 0;
+    for (int i = lane; i < O - S; i += WAVE / EPW) {
         float x = s.u.post.obs_tmp[off + i];
         if (T.add_noise) x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, i) - 1.f) * T.noise_vec[i];
         if (T.obs_layout == LGS_OBS_HANDSTAND) {
@@ -2488,8 +2495,26 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         E.obs[(size_t)O * e + i] = clipf(x, -T.clip_observations, T.clip_observations);
     }
     if (P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID)
-        for (int i = lane; i < P; i += WAVE / EPW)
+        for (int i = lane; i < P - S; i += WAVE / EPW)
             E.priv_obs[(size_t)P * e + i] = clipf(s.u.post.obs_tmp[i], -T.clip_observations, T.clip_observations);
+    if (S > 0) {
+        // legged_gym's compute_observations tail (include/leggedsim.h, lgs_height_obs): the scan
+        // the prepare part measured before the reset against the root after it, straight from
+        // the env buffer to the rows.  Lane l takes the points height_scan gave it (k = l,
+        // l + WAVE / EPW, ...): in the one-launch step it reads back its own stores.
+        const TerrainTail& X = terrain_tail(T);
+        const float* mh = X.heights + (size_t)S * e;
+        const float rz = s.root[2] - X.obs_offset;
+        const bool priv = P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID;
+        for (int k = lane; k < S; k += WAVE / EPW) {
+            const float h = clipf(rz - mh[k], -X.obs_clip, X.obs_clip) * X.obs_scale;
+            float x = h;
+            if (T.add_noise)
+                x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, O - S + k) - 1.f) * X.obs_noise;
+            E.obs[(size_t)O * e + (O - S) + k] = clipf(x, -T.clip_observations, T.clip_observations);
+            if (priv) E.priv_obs[(size_t)P * e + (P - S) + k] = clipf(h, -T.clip_observations, T.clip_observations);
+        }
+    }
     // bookkeeping (:707-709)
     if (lane < A) E.last_actions[A * e + lane] = act[lane];
     if (lane < Ad) E.last_dof_vel[Ad * e + lane] = s.qd[lane];
@@ -2740,6 +2765,10 @@ struct lgs_sim {
     float4* self_mem = nullptr;
     int has_task = 0;
     int task_curriculum = 0, task_heights = 0;  // the task's rough-terrain switches (env buffers checked per call)
+    // what check_obs_width compares: the task's row widths, layout, action count and scan grid,
+    // and the height observations (lgs_set_height_observations)
+    int task_obs = 0, task_priv = 0, task_layout = 0, task_actions = 0, task_scan = 0;
+    lgs_height_obs hobs{};
     float hf_hs = 0.f;           // the heightfield's horizontal scale (TerrainTail::hf_hs)
     TerrainTail tail_host{};     // what the device block after task_dev holds (sync_terrain_tail)
     int rows = 32;
@@ -3315,7 +3344,10 @@ LGS_API int lgs_set_dof_state_indexed(lgs_sim* s, const float* src, const int32_
 LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     if (!s || !t) return set_err(LGS_ERR_ARG, "null argument");
     if (t->num_actions != s->D) return set_err(LGS_ERR_ARG, "lgs_set_task: num_actions must equal num_dofs");
-    if (t->num_obs > LGS_MAX_OBS || t->num_privileged_obs > LGS_MAX_OBS || t->num_rewards > LGS_MAX_REWARDS ||
+    // (the rows may carry the height scan after a head of <= LGS_MAX_OBS entries: the step entry
+    // points check the widths against lgs_set_height_observations, check_obs_width)
+    if (t->num_obs < 0 || t->num_privileged_obs < 0 || t->num_obs > LGS_MAX_OBS + LGS_MAX_SCAN_OBS ||
+        t->num_privileged_obs > LGS_MAX_OBS + LGS_MAX_SCAN_OBS || t->num_rewards > LGS_MAX_REWARDS ||
         t->num_extra_sums < 0 || t->num_rewards + 1 + t->num_extra_sums > WAVE - 1)
         return set_err(LGS_ERR_ARG, "lgs_set_task: obs/reward counts exceed limits");
     if (t->num_feet > LGS_MAX_FEET || t->resample_interval <= 0 || t->push_interval <= 0 || t->decimation <= 0)
@@ -3350,6 +3382,48 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     s->has_task = 1;
     s->task_curriculum = t->terrain_curriculum != 0;
     s->task_heights = t->measure_heights != 0;
+    s->task_obs = t->num_obs; s->task_priv = t->num_privileged_obs; s->task_layout = t->obs_layout;
+    s->task_actions = t->num_actions;
+    s->task_scan = t->measure_heights ? t->num_height_x * t->num_height_y : 0;
+    return LGS_OK;
+}
+
+LGS_API int lgs_set_height_observations(lgs_sim* s, const lgs_height_obs* d) {
+    if (!s) return set_err(LGS_ERR_ARG, "lgs_set_height_observations: null argument");
+    lgs_height_obs v{};
+    if (d && d->enabled) {
+        if (!(d->clip > 0.f) || !(d->scale == d->scale) || !(d->offset == d->offset) || !(d->noise_scale >= 0.f))
+            return set_err(LGS_ERR_ARG, "lgs_set_height_observations: clip > 0, noise_scale >= 0, finite offset and scale");
+        v = *d;
+        v.enabled = 1;
+    }
+    s->hobs = v;
+    return LGS_OK;
+}
+
+// The observation rows' widths against the height observations (the two setters may come in
+// either order, so every step / reset entry point checks the pair before it launches anything):
+// without the scan tail the rows fit LGS_MAX_OBS; with it they are exactly the layout's head
+// plus the scan's points.
+static int check_obs_width(lgs_sim* s, const char* what) {
+    if (!s->hobs.enabled) {
+        if (s->task_obs > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS)
+            return set_err(LGS_ERR_ARG, std::string(what) + ": obs counts exceed LGS_MAX_OBS (no height observations set)");
+        return LGS_OK;
+    }
+    const int P = s->task_scan, A = s->task_actions;
+    if (P < 1) return set_err(LGS_ERR_ARG, std::string(what) + ": height observations need the task's measure_heights");
+    if (P > LGS_MAX_SCAN_OBS)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": height observations: more than LGS_MAX_SCAN_OBS scan points");
+    if (s->task_layout != LGS_OBS_QUADRUPED && s->task_layout != LGS_OBS_HUMANOID)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": height observations need the quadruped or humanoid layout");
+    const bool hum = s->task_layout == LGS_OBS_HUMANOID;
+    const int head = hum ? 11 + 3 * A : 12 + 3 * A, head_priv = 14 + 3 * A;
+    if (head_priv > LGS_MAX_OBS || s->task_obs != head + P || (hum && s->task_priv != 0 && s->task_priv != head_priv + P) ||
+        (!hum && s->task_priv > LGS_MAX_OBS))
+        return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " / num_privileged_obs " +
+                       std::to_string(s->task_priv) + " do not match the layout's head (" + std::to_string(head) +
+                       (hum ? " / " + std::to_string(head_priv) : std::string()) + ") + " + std::to_string(P) + " scan points");
     return LGS_OK;
 }
 
@@ -3363,6 +3437,10 @@ static int sync_terrain_tail(lgs_sim* s, const lgs_env_buffers* env) {
     v.heights = env->measured_heights; v.hf_hs = s->hf_hs;
     v.hf = s->sp.hf; v.hf_rows = s->sp.hf_rows; v.hf_cols = s->sp.hf_cols;
     v.hf_inv_hs = s->sp.hf_inv_hs; v.hf_vs = s->sp.hf_vs; v.hf_border = s->sp.hf_border;
+    if (s->hobs.enabled) {
+        v.obs_scan = s->task_scan; v.obs_offset = s->hobs.offset; v.obs_clip = s->hobs.clip;
+        v.obs_scale = s->hobs.scale; v.obs_noise = s->hobs.noise_scale;
+    }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s->stream, &cap);
     // (inside a capture the launch is always recorded: a replay must not depend on what an
@@ -3378,6 +3456,7 @@ static int sync_terrain_tail(lgs_sim* s, const lgs_env_buffers* env) {
 // the env buffers a rough-terrain switch of the task needs (a missing one is an error, not a
 // skip), then into the device block the step reads them from
 static int check_terrain_buffers(lgs_sim* s, const lgs_env_buffers* env, const char* what) {
+    if (const int rc = check_obs_width(s, what)) return rc;
     if (s->task_curriculum && (!env->terrain_levels || !env->terrain_types || !env->terrain_origins))
         return set_err(LGS_ERR_ARG, std::string(what) + ": terrain_curriculum needs terrain_levels, terrain_types, terrain_origins");
     if (s->task_heights && !env->measured_heights)
@@ -3457,6 +3536,7 @@ LGS_API int lgs_post_physics_term_rewards(lgs_sim* s, const lgs_env_buffers* env
 LGS_API int lgs_reset_all(lgs_sim* s, const lgs_env_buffers* env, int64_t step_counter) {
     if (!s || !env) return set_err(LGS_ERR_ARG, "null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_all: state not bound or task not set");
+    if (const int rc = check_obs_width(s, "lgs_reset_all")) return rc;
     DevState st = state_of(s);
     if (pick(s) == V_EXTRA) {
         const int rc = extra_reset(s, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, nullptr);

@@ -1789,6 +1789,7 @@ __global__ __launch_bounds__(PMLP_OPT_THREADS) void k_adam_vec(float* __restrict
 // (k_gemm_nt): the result is bitwise the same.
 #define FMLP_MAX_H0 512
 #define FMLP_MAX_H1 256
+#define FMLP_MAX_K0 256  // the input rows are staged in Y1 (row stride FMLP_MAX_H1 + 8)
 #define FMLP_THREADS 512
 
 struct FmlpJob {
@@ -1800,7 +1801,7 @@ struct FmlpJob {
     const bf16* W[4];       // W[l] = [N[l], K_l] bf16, ld K_l (K_0 = K0, K_l = N[l-1])
     const float* b[4];
     int N[4];
-    int K0;                 // padded input width, a multiple of 16, <= 64
+    int K0;                 // padded input width, a multiple of 16, <= FMLP_MAX_K0
     bf16* y[3];             // optional hidden outputs [M, N[l]] (ld ldy[l])
     int ldy[3];
     float* out;             // fp32 [M, N[3]] (ld ldo)
@@ -2087,16 +2088,19 @@ __device__ void roll_epilogue(const FmlpJob& J, int jj, const RollStep& rs, int 
 
 // LOSS: the update's PPO loss on the workgroup's rows after both nets (loss_quad_rows; the
 // workgroup runs every job, gridDim.y == 1), its partial sums in row blockIdx.x
-template <int R, bool ROLL = false, bool LOSS = false>
+// WIDE (the 96-row form at K0 > 64, which X cannot hold): x is staged in Y1 there too -- it is
+// dead once layer 0 has written Y0 -- and gathered again for a second job; the narrow
+// instantiations are the code they were
+template <int R, bool ROLL = false, bool LOSS = false, bool WIDE = false>
 __global__ __launch_bounds__(FMLP_THREADS) void k_mlp_fwd(FmlpJobs jobs, int M, RollStep rs, LossArgs la = {},
                                                          LossStepOut lo = {}) {
     // y0 (then y2) and x (then y1); row strides 8 elements past the width: ds_read_b128
     // fragment reads of 32 consecutive rows hit 4-bank groups 4 apart (conflict-free)
     constexpr int LD0 = FMLP_MAX_H0 + 8, LD1 = FMLP_MAX_H1 + 8;
-    // the 96-row form keeps the input rows in a region of their own (LDX = 64 + 4: the 160 KB
-    // hold it), so a second job on the same rows (the critic on the actor's observations)
+    // the 96-row form keeps input rows of up to 64 columns in a region of their own (LDX = 64 + 4:
+    // the 160 KB hold it), so a second job on the same rows (the critic on the actor's observations)
     // does not gather them again; the 32-row form stages them in Y1 (3 workgroups per CU)
-    constexpr bool XR = R >= 96;
+    constexpr bool XR = R >= 96 && !WIDE;
     constexpr int LDX = 68;
     __shared__ __attribute__((aligned(16))) bf16 Y0[R * LD0];
     __shared__ __attribute__((aligned(16))) bf16 Y1[R * LD1];
@@ -2953,8 +2957,8 @@ static int fmlp_pack(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, Fml
         const std::string w = "pmlp_mlp_forward job " + std::to_string(i) + ": ";
         if (!J.x || J.kx <= 0 || J.ldx < J.kx || (J.ldx % 4 == 0 && ((uintptr_t)J.x & 15)) || ((uintptr_t)J.x & 3))
             return fail(-1, w + "x: 0 < kx <= ldx, 16-byte aligned when ldx is a multiple of 4");
-        if (J.K0 <= 0 || J.K0 % 16 || J.K0 > 64 || J.kx > J.K0)
-            return fail(-1, w + "K0 must be a multiple of 16, kx <= K0 <= 64");
+        if (J.K0 <= 0 || J.K0 % 16 || J.K0 > FMLP_MAX_K0 || J.kx > J.K0)
+            return fail(-1, w + "K0 must be a multiple of 16, kx <= K0 <= 256");
         if (J.xa && (J.ldxa < J.K0 || J.ldxa % 8 || !al16(J.xa))) return fail(-1, w + "xa: ldxa >= K0, a multiple of 8");
         const int lim[3] = {FMLP_MAX_H0, FMLP_MAX_H1, FMLP_MAX_H0};
         for (int l = 0; l < 4; ++l) {
@@ -2977,6 +2981,13 @@ static int fmlp_pack(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, Fml
     return 0;
 }
 
+// a job's input rows are wider than the 96-row form's own x region
+static bool fmlp_wide(const FmlpJobs& fj) {
+    for (int i = 0; i < fj.njobs; ++i)
+        if (fj.j[i].K0 > 64) return true;
+    return false;
+}
+
 PMLP_API int pmlp_mlp_forward(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, void* stream) {
     FmlpJobs fj;
     if (int e = fmlp_pack(njobs, jobs, M, fj)) return e;
@@ -2984,7 +2995,10 @@ PMLP_API int pmlp_mlp_forward(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32
     // mini-batches; 32 with one job per workgroup for the rollout's num_envs rows
     hipStream_t st = (hipStream_t)stream;
     const RollStep none{};
-    if (M >= 96 * 192)
+    if (M >= 96 * 192 && fmlp_wide(fj))
+        hipLaunchKernelGGL((k_mlp_fwd<96, false, false, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0, st, fj, M,
+                           none);
+    else if (M >= 96 * 192)
         hipLaunchKernelGGL((k_mlp_fwd<96>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0, st, fj, M, none);
     else
         hipLaunchKernelGGL((k_mlp_fwd<32>), dim3((M + 31) / 32, njobs), dim3(FMLP_THREADS), 0, st, fj, M, none);
@@ -3179,8 +3193,12 @@ PMLP_API int pmlp_mlp_forward_ppo_loss(const pmlp_mlp_fwd_job* jobs, int32_t M, 
         return fail(-1, "pmlp_mlp_forward_ppo_loss: null output or padded width too small");
     LossStepOut o{partial, (bf16*)dmu, (bf16*)dmu_t, (bf16*)dvalue, (bf16*)dvalue_t, Ap, Vp, nullptr, nullptr};
     const RollStep none{};
-    hipLaunchKernelGGL((k_mlp_fwd<96, false, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0,
-                       (hipStream_t)stream, fj, M, none, a, o);
+    if (fmlp_wide(fj))
+        hipLaunchKernelGGL((k_mlp_fwd<96, false, true, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0,
+                           (hipStream_t)stream, fj, M, none, a, o);
+    else
+        hipLaunchKernelGGL((k_mlp_fwd<96, false, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0,
+                           (hipStream_t)stream, fj, M, none, a, o);
     PMLP_CHECK_LAUNCH("pmlp_mlp_forward_ppo_loss");
     return 0;
 }

@@ -118,4 +118,8 @@ def noise_scale_vec(cfg, num_obs, A, obs_layout):
         v[3:6] = ns.gravity * lvl
         v[9:9 + A] = ns.dof_pos * lvl * sc.dof_pos
         v[9 + A:9 + 2 * A] = ns.dof_vel * lvl * sc.dof_vel
+    # the height scan after the head (legged_robot.py:216-218), when it is observed
+    if getattr(cfg.terrain, "scan_in_observations", False) and obs_layout != cabi.OBS_HANDSTAND:
+        P = len(cfg.terrain.measured_points_x) * len(cfg.terrain.measured_points_y)
+        v[max(num_obs - P, 0):] = ns.height_measurements * lvl * sc.height_measurements
     return v

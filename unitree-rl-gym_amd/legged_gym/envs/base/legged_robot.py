@@ -30,7 +30,7 @@ from legged_gym.utils.helpers import class_to_dict
 from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
-from leggedsim.task import build_task_params, terrain_switches
+from leggedsim.task import build_task_params, check_scan_observations, height_obs_params, terrain_switches
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -205,6 +205,9 @@ class LeggedRobot(BaseTask):
         # the rough-terrain switches; refused on a plane, and the ground-relative
         # height terms without the scan
         self.level_curriculum, self.scan_heights, self.ground_relative_heights = terrain_switches(self.cfg)
+        # the scan as the tail of the observation rows: needs the scan, a layout with a
+        # tail and num_observations = the layout's head + the scan's points
+        self.num_scan_obs = check_scan_observations(self.cfg, self.obs_layout, self.cfg.env.num_actions)
 
     # ------------------------------------------------------------- sim ------
     def create_sim(self):
@@ -473,6 +476,8 @@ class LeggedRobot(BaseTask):
             raise ValueError(f"_get_noise_scale_vec returned {nvec.numel()} entries for {self.num_obs} observations")
         self.task_params = build_task_params(self)
         self.sim.set_task(self.task_params)
+        self.height_obs = height_obs_params(self)
+        self.sim.set_height_observations(self.height_obs)
         self._env_structs = [self._make_env_struct(i) for i in range(2)]
         self._bound = {name: getattr(self, name) for name in self.CALLBACK_BUFFERS}
         self._split_step = bool(self._py_rewards or self._hooks)

@@ -41,6 +41,11 @@ class LeggedRobotCfg(BaseConfig):
         level_curriculum = False
         # scan_heights: env.measured_heights [N, len(x) * len(y)] of measured_points_x / _y every step
         scan_heights = False
+        # scan_in_observations (needs scan_heights): the scan is the tail of the observation
+        # rows, legged_gym's clip(root_z - 0.5 - measured_heights, -1, 1) * obs_scales.height_measurements;
+        # env.num_observations (and num_privileged_obs of the humanoid layout) then count the
+        # len(x) * len(y) points after the layout's own entries.  (measure_heights above is inert.)
+        scan_in_observations = False
 
     class commands:
         curriculum = False

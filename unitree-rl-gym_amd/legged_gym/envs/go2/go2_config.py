@@ -43,6 +43,24 @@ class GO2RoughCfg(LeggedRobotCfg):
             pgs_sweeps = 5
 
 
+class GO2TerrainCfg(GO2RoughCfg):
+    """go2_terrain: legged_gym's rough-terrain task on the fused step: the
+    curriculum heightfield, the level curriculum at reset, the 17 x 11 height scan as the tail of
+    the observation row (48 + 187 = 235 policy inputs) and base_height measured from the ground."""
+
+    class env(GO2RoughCfg.env):
+        num_observations = 235
+
+    class terrain(GO2RoughCfg.terrain):
+        mesh_type = "heightfield"
+        level_curriculum = True
+        scan_heights = True
+        scan_in_observations = True
+
+    class rewards(GO2RoughCfg.rewards):
+        ground_relative_heights = True
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -50,3 +68,8 @@ class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class runner(LeggedRobotCfgPPO.runner):
         run_name = ""
         experiment_name = "rough_go2"
+
+
+class GO2TerrainCfgPPO(GO2RoughCfgPPO):
+    class runner(GO2RoughCfgPPO.runner):
+        experiment_name = "go2_terrain"

@@ -52,6 +52,8 @@ def reward_id(name, task_aliases=None):
 STREAM_NOISE, STREAM_CMD, STREAM_RESET_DOF, STREAM_RESET_ROOT, STREAM_RESET_CMD, STREAM_PUSH = range(6)
 STREAM_TERRAIN = 6  # the level curriculum's graduation draw
 MAX_HEIGHT_POINTS = 32
+MAX_SCAN_OBS = 256  # scan points the observation rows may carry after the head (lgs_set_height_observations)
+HEIGHT_OBS_OFFSET, HEIGHT_OBS_CLIP = 0.5, 1.0  # legged_gym's compute_observations: clip(root_z - 0.5 - heights, -1, 1)
 
 f32p = C.POINTER(C.c_float)
 i32p = C.POINTER(C.c_int32)
@@ -94,6 +96,12 @@ class SelfCollisionHandle:
         self.desc = SelfCollisionDesc(len(self.body), self.body.ctypes.data_as(i32p), self.caps.ctypes.data_as(f32p),
                                       len(self.pairs) // 2, self.pairs.ctypes.data_as(i32p),
                                       int(sc.max_self_contacts))
+
+
+class HeightObs(C.Structure):
+    """lgs_height_obs: the height scan as the tail of the observation rows."""
+    _fields_ = [("enabled", C.c_int32), ("offset", C.c_float), ("clip", C.c_float), ("scale", C.c_float),
+                ("noise_scale", C.c_float)]
 
 
 class TaskParams(C.Structure):

@@ -78,6 +78,7 @@ def load():
     lib.lgs_get_counts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.lgs_set_heightfield.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float]
     lib.lgs_set_self_collision.argtypes = [vp, C.POINTER(cabi.SelfCollisionDesc)]
+    lib.lgs_set_height_observations.argtypes = [vp, C.POINTER(cabi.HeightObs)]
     if hasattr(lib, "lgs_get_contact_stats"):  # (absent only from pre-round-4 builds used in A/B timing)
         lib.lgs_get_contact_stats.argtypes = [vp, vp, C.c_int32]
         lib.lgs_get_contact_stats.restype = C.c_int
@@ -99,7 +100,7 @@ def load():
                  "lgs_set_task", "lgs_step", "lgs_reset_all", "lgs_get_counts", "lgs_set_heightfield",
                  "lgs_step_physics", "lgs_post_physics", "lgs_reset_idx", "lgs_post_physics_rewards",
                  "lgs_post_physics_finish", "lgs_post_physics_prepare", "lgs_post_physics_term_rewards",
-                 "lgs_set_self_collision"):
+                 "lgs_set_self_collision", "lgs_set_height_observations"):
         getattr(lib, name).restype = C.c_int
     _LIB = lib
     return lib
@@ -119,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "lgs_post_physics_prepare", "lgs_post_physics_term_rewards",
     "lgs_step_deferred", "lgs_step_extras", "lgs_get_push_state",
     "lgs_set_self_collision", "lgs_get_body_name", "lgs_get_dof_name", "lgs_find_body", "lgs_find_dof",
-    "lgs_get_contact_stats", "lgs_get_instantiation", "lgs_get_factor_chain",
+    "lgs_get_contact_stats", "lgs_get_instantiation", "lgs_get_factor_chain", "lgs_set_height_observations",
 ]
 
 
@@ -170,6 +171,12 @@ class Sim:
             return
         self._sc = cabi.SelfCollisionHandle(sc)
         check(self.lib, self.lib.lgs_set_self_collision(self.handle, C.byref(self._sc.desc)), "lgs_set_self_collision")
+
+    def set_height_observations(self, desc):
+        """The height scan as the tail of the observation rows (a cabi.HeightObs; None: off)."""
+        self._hobs = desc
+        check(self.lib, self.lib.lgs_set_height_observations(self.handle, None if desc is None else C.byref(desc)),
+              "lgs_set_height_observations")
 
     def bind(self, root, dofs, cforce, rbs):
         for t in (root, dofs, cforce, rbs):

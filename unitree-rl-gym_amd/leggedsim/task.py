@@ -55,7 +55,9 @@ def build_task_params(env) -> cabi.TaskParams:
     T.obs_scale_dof_pos, T.obs_scale_dof_vel = s.dof_pos, s.dof_vel
     _put(T.commands_scale, env.commands_scale)
     T.add_noise = int(bool(env.add_noise))
-    _put(T.noise_vec, env.noise_scale_vec)
+    # (with the height scan observed the vector's tail is the scan's one scale, in lgs_height_obs:
+    # height_obs_params, which also refuses a cfg the tail cannot honour)
+    _put(T.noise_vec, _np(env.noise_scale_vec).reshape(-1)[:env.num_obs - height_obs_params(env).num_points])
     T.max_episode_length = float(env.max_episode_length)
     T.max_episode_length_s = float(env.max_episode_length_s)
     T.resample_interval = int(cfg.commands.resampling_time / env.dt)
@@ -146,6 +148,65 @@ def terrain_switches(cfg):
     if rel and not scan:
         raise ValueError("rewards.ground_relative_heights needs terrain.scan_heights (base_height averages the scan)")
     return cur, scan, rel
+
+
+def scan_in_observations(cfg):
+    """terrain.scan_in_observations of a cfg (the height scan is the tail of the
+    observation rows), refusing it without the scan it observes.  (terrain.measure_heights is
+    True in every config and inert: it is not the switch.)"""
+    on = bool(getattr(cfg.terrain, "scan_in_observations", False))
+    if on and not terrain_switches(cfg)[1]:
+        raise ValueError("terrain.scan_in_observations needs terrain.scan_heights (the scan it observes)")
+    return on
+
+
+def layout_head(obs_layout, A):
+    """(observation, privileged observation) widths of a layout's own rows for A actions."""
+    if obs_layout == cabi.OBS_QUADRUPED:
+        return 12 + 3 * A, 0
+    if obs_layout == cabi.OBS_HUMANOID:
+        return 11 + 3 * A, 14 + 3 * A
+    raise ValueError("terrain.scan_in_observations needs the quadruped or the humanoid observation layout")
+
+
+def check_scan_observations(cfg, obs_layout, A):
+    """The constructor's checks of terrain.scan_in_observations: the layout, the grid's size and
+    cfg.env.num_observations / num_privileged_obs = the layout's head + the scan's points.
+    Returns the number of scan points in the rows (0: the switch is off)."""
+    if not scan_in_observations(cfg):
+        return 0
+    head, head_priv = layout_head(obs_layout, A)
+    tc = cfg.terrain
+    P = len(tc.measured_points_x) * len(tc.measured_points_y)
+    if not 1 <= P <= cabi.MAX_SCAN_OBS:
+        raise ValueError(f"terrain.scan_in_observations: {P} scan points, the rows take 1 to {cabi.MAX_SCAN_OBS}")
+    if cfg.env.num_observations != head + P:
+        raise ValueError(f"terrain.scan_in_observations: env.num_observations must be {head} + {P} scan points = "
+                         f"{head + P}, not {cfg.env.num_observations}")
+    priv = cfg.env.num_privileged_obs
+    if priv and head_priv and priv != head_priv + P:
+        raise ValueError(f"terrain.scan_in_observations: env.num_privileged_obs must be {head_priv} + {P} scan points "
+                         f"= {head_priv + P}, not {priv}")
+    return P
+
+
+def height_obs_params(env) -> cabi.HeightObs:
+    """lgs_height_obs of an env: off, or legged_gym's tail constants and the one noise scale of
+    the tail of env.noise_scale_vec (a task override that makes it non-uniform is refused)."""
+    H = cabi.HeightObs()
+    P = check_scan_observations(env.cfg, env.obs_layout, env.num_actions)
+    H.num_points = P  # (not a field of the C struct)
+    if not P:
+        return H
+    tail = _np(env.noise_scale_vec).astype(np.float32).reshape(-1)[env.num_obs - P:]
+    if len(tail) != P or not (tail == tail[0]).all():
+        raise ValueError("_get_noise_scale_vec: the height scan's entries must share one noise scale "
+                         "(the kernel's tail has a single scale)")
+    H.enabled = 1
+    H.offset, H.clip = cabi.HEIGHT_OBS_OFFSET, cabi.HEIGHT_OBS_CLIP
+    H.scale = float(env.obs_scales.height_measurements)
+    H.noise_scale = float(tail[0])
+    return H
 
 
 def _terrain_switches(T, env):

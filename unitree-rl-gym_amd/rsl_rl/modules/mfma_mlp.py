@@ -210,8 +210,8 @@ def supported(seq):
 
 def mlp_forward_supported(lins, k0p):
     """pmlp_mlp_forward's shape limits (include/ppo_mlp.h): 4 Linear layers, K0 a multiple
-    of 16 (<= 64), hidden widths multiples of 32 (<= 512 / 256 / 512), output <= 32."""
-    if len(lins) != 4 or k0p % 16 or k0p > 64:
+    of 16 (<= 256), hidden widths multiples of 32 (<= 512 / 256 / 512), output <= 32."""
+    if len(lins) != 4 or k0p % 16 or k0p > 256:
         return False
     lim = (512, 256, 512)
     return all(lins[l].out_features % 32 == 0 and lins[l].out_features <= lim[l] for l in range(3)) and \
