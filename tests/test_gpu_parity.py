@@ -310,6 +310,22 @@ def test_fused_step_matches_oracle_bitwise_edge_and_full_sizes(task, n):
     fused_vs_oracle(env, g, 2, f"{task} x{n}")
 
 
+@pytest.mark.parametrize("task,n", [("go2", 6), ("h1", 5), ("g1", 4), ("go2", 4098)])
+def test_exact_48_row_kernels_match_oracle_bitwise(task, n, monkeypatch):
+    """The registry's robots on their exact-shape 48-row kernels (12 contact slots, one env per
+    wave), which no registered task selects: the three shapes on the 4 waves/SIMD build of
+    k_step (<= 4096 envs), and Go2 at the smallest even env count on the default build."""
+    cls = task_registry.get_task_class(task)
+    monkeypatch.setattr(cls, "max_contacts", 12)
+    monkeypatch.setattr(cls, "max_rows", 48)
+    env, g = warm(task, n, steps=8, seed=n)
+    rows = C.c_int32()
+    assert env.sim.lib.lgs_get_instantiation(env.sim.handle, None, None, C.byref(rows)) == 0
+    assert rows.value == 48
+    assert env.sim.factor_chain() == {"go2": 3, "h1": 5, "g1": 6}[task]
+    fused_vs_oracle(env, g, 2, f"{task} x{n} 48 rows")
+
+
 @pytest.mark.parametrize("task", ["go2", "g1_rough"])
 def test_heightfield_step_matches_oracle_bitwise(task):
     env, g = warm(task, 512, terrain__mesh_type="heightfield", terrain__num_rows=5, terrain__num_cols=8)

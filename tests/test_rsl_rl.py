@@ -283,3 +283,31 @@ def test_fused_recurrent_covers_only_head_widths_the_kernels_take(hid, ok):
     ac = ActorCriticRecurrent(47, 50, 12, actor_hidden_dims=hid, critic_hidden_dims=hid, rnn_type="lstm",
                               rnn_hidden_size=64, rnn_num_layers=1)
     assert fused_recurrent.supported(ac, 256, 4) is ok
+
+
+def test_capture_without_gc_collects_first_and_holds_the_collector_off():
+    """The graph captures run under capture_without_gc: cyclic garbage whose finalizer issues
+    HIP calls (an earlier env's simulator) is finalized before the capture begins, none is
+    collected inside it, and the collector is back afterwards, also when the capture raises."""
+    import gc
+    from rsl_rl.utils import capture_without_gc
+    done = []
+
+    class Cyclic:
+        def __init__(self, tag):
+            self.me, self.tag = self, tag
+
+        def __del__(self):
+            done.append(self.tag)
+
+    Cyclic("before")
+    with capture_without_gc():
+        assert done == ["before"] and not gc.isenabled()
+        Cyclic("inside")
+        [[] for _ in range(5000)]  # enough allocations for an automatic collection, were it on
+        assert done == ["before"]
+    assert gc.isenabled()
+    with pytest.raises(RuntimeError):
+        with capture_without_gc():
+            raise RuntimeError("capture failed")
+    assert gc.isenabled()

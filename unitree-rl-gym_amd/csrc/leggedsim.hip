@@ -305,9 +305,12 @@ __device__ __forceinline__ float rand_range(float lo, float hi, float u) { retur
 // (terrain_utils.convert_heightfield_to_trimesh); outside the map the edge samples
 // continue.  Without a heightfield: the plane z = 0, normal +z.  Same arithmetic
 // as oracle/lgs_oracle.c terrain_sample().
-__device__ __forceinline__ float terrain_sample(const DevSim& sp, float x, float y, float* nrm) {
+// Map: whichever block holds the map, DevSim or the post-physics stages' TerrainTail (which
+// take the height alone: NORMAL = false, nrm unused).
+template <bool NORMAL = true, class Map>
+__device__ __forceinline__ float terrain_sample(const Map& sp, float x, float y, float* nrm) {
     if (!sp.hf) {
-        nrm[0] = 0.f; nrm[1] = 0.f; nrm[2] = 1.f;
+        if constexpr (NORMAL) { nrm[0] = 0.f; nrm[1] = 0.f; nrm[2] = 1.f; }
         return 0.f;
     }
     float u = (x + sp.hf_border) * sp.hf_inv_hs, v = (y + sp.hf_border) * sp.hf_inv_hs;
@@ -322,9 +325,11 @@ __device__ __forceinline__ float terrain_sample(const DevSim& sp, float x, float
     if (fu >= fv) { du = h10 - h00; dv = h11 - h10; }
     else { du = h11 - h01; dv = h01 - h00; }
     const float h = h00 + fu * du + fv * dv;
-    const float gx = du * sp.hf_inv_hs, gy = dv * sp.hf_inv_hs;
-    const float inv = 1.f / sqrtf(gx * gx + gy * gy + 1.f);
-    nrm[0] = 0.f - gx * inv; nrm[1] = 0.f - gy * inv; nrm[2] = inv;
+    if constexpr (NORMAL) {
+        const float gx = du * sp.hf_inv_hs, gy = dv * sp.hf_inv_hs;
+        const float inv = 1.f / sqrtf(gx * gx + gy * gy + 1.f);
+        nrm[0] = 0.f - gx * inv; nrm[1] = 0.f - gy * inv; nrm[2] = inv;
+    }
     return h;
 }
 // contact frame: t1 = normalise(e_x - n_x n), t2 = n x t1 (flat ground: +x, +y exactly)
@@ -398,6 +403,20 @@ __device__ __forceinline__ unsigned chunk_bodies(const ModelCache<D, B>& mc, int
     return EPW == 2 ? mc.ch32[ch] : (mc.ch32[2 * ch] | mc.ch32[2 * ch + 1]);
 }
 
+// Smem::u.post.misc, the post-physics stages' scalars: where each starts.  The three
+// base-frame vectors are consecutive (their lanes and the observation head index across them).
+enum {
+    MI_LIN_VEL = 0,       // base linear velocity (3)
+    MI_ANG_VEL = 3,       // base angular velocity (3)
+    MI_GRAVITY = 6,       // projected gravity (3)
+    MI_PHASE = 9,         // gait phase
+    MI_LEG_PHASE = 10,    // the two legs' phases (2)
+    MI_CMD = 12,          // commands (4)
+    MI_CLEARANCE = 16,    // ground_relative_heights: the mean of root_z - measured_heights
+    MI_FOOT_GROUND = 17,  // ground_relative_heights: the ground under foot f (LGS_MAX_FEET)
+    MI_COUNT = MI_FOOT_GROUND + LGS_MAX_FEET
+};
+
 template <int D, int B, int ROWS>
 struct Smem {
     static constexpr int n = 6 + D;
@@ -427,7 +446,8 @@ struct Smem {
         } fk;
         struct {  // post-physics scratch
             float obs_tmp[LGS_MAX_OBS];
-            float misc[32];
+            float misc[32];  // (MI_*)
+            static_assert(MI_COUNT <= 32, "misc holds every MI_* slot");
             // reward staging: row k holds the per-DOF / per-foot elements of active term k,
             // which lane k then adds in index order (EL: the longest such list)
             float el[LGS_MAX_REWARDS][EL];
@@ -1877,7 +1897,7 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
     constexpr int EL = Smem<D, B, ROWS>::EL;
     const int lane = hl<EPW>();
     const int A = T.num_actions, nr = T.num_rewards, nf = T.num_feet;
-    const float* mi = s.u.post.misc;  // bl 0-2, ba 3-5, pg 6-8, phase 9, leg_phase 10-11, cmd 12-15
+    const float* mi = s.u.post.misc;
     const int jl = lane < A ? lane : 0;
     const float q = s.q[jl], qd = s.qd[jl], tau = s.tau[jl], act = s.act[jl];
     const float last_act = s.pre.last_act[jl], last_qd = s.pre.last_qd[jl];
@@ -1919,7 +1939,7 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
             v = fmaxf(sqrtf(F0 * F0 + F1 * F1 + F2 * F2) - T.max_contact_force, 0.f);
             break;
         case LGS_REW_CONTACT: {
-            const int stance = mi[10 + (lane < nf ? lane : 0)] < T.stance_threshold;
+            const int stance = mi[MI_LEG_PHASE + (lane < nf ? lane : 0)] < T.stance_threshold;
             const int contact = F2 > 1.f;
             v = (contact == stance) ? 1.f : 0.f;
         } break;
@@ -1927,7 +1947,7 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
             if (lane < nf) {
                 const int contact = sqrtf(F0 * F0 + F1 * F1 + F2 * F2) > 1.f;
                 float fz = rbs[13 * in.fb + 2];
-                if (T.ground_relative_heights) fz = fz - mi[17 + lane];  // (above the ground under the foot)
+                if (T.ground_relative_heights) fz = fz - mi[MI_FOOT_GROUND + lane];  // (above the ground under the foot)
                 const float d = fz - T.swing_height_target;
                 v = d * d * (contact ? 0.f : 1.f);
             }
@@ -1965,10 +1985,10 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
         float sum = 0.f;
 #pragma unroll
         for (int j = 0; j < EL; ++j) sum = j < cnt ? sum + v[j] : sum;
-        const float* bl = mi;
-        const float* ba = mi + 3;
-        const float* pg = mi + 6;
-        const float* cmd = mi + 12;
+        const float* bl = mi + MI_LIN_VEL;
+        const float* ba = mi + MI_ANG_VEL;
+        const float* pg = mi + MI_GRAVITY;
+        const float* cmd = mi + MI_CMD;
         float x = 0.f;  // the tracking terms' squared error
         bool track = false;
         switch (in.id) {
@@ -1977,7 +1997,7 @@ __device__ __forceinline__ float reward_terms(Smem<D, B, ROWS>& s, const lgs_tas
         case LGS_REW_ORIENTATION: r = pg[0] * pg[0] + pg[1] * pg[1]; break;
         case LGS_REW_BASE_HEIGHT: {
             float z = s.root[2];
-            if (T.ground_relative_heights) z = mi[16];  // (the mean height above the scanned ground)
+            if (T.ground_relative_heights) z = mi[MI_CLEARANCE];  // (the mean height above the scanned ground)
             float d = z - T.base_height_target; r = d * d;
         } break;
         case LGS_REW_TRACKING_LIN_VEL: {
@@ -2069,22 +2089,6 @@ struct TerrainTail {
     int obs_scan;
     float obs_offset, obs_clip, obs_scale, obs_noise;
 };
-// terrain_sample's height (same arithmetic, no normal) on the block's copy of the map
-__device__ __forceinline__ float tail_ground(const TerrainTail& X, float x, float y) {
-    if (!X.hf) return 0.f;
-    float u = (x + X.hf_border) * X.hf_inv_hs, v = (y + X.hf_border) * X.hf_inv_hs;
-    u = fminf(fmaxf(u, 0.f), (float)(X.hf_rows - 1));
-    v = fminf(fmaxf(v, 0.f), (float)(X.hf_cols - 1));
-    const int i = min((int)u, X.hf_rows - 2), j = min((int)v, X.hf_cols - 2);
-    const float fu = u - (float)i, fv = v - (float)j;
-    const int16_t* h0 = X.hf + (size_t)i * X.hf_cols + j;
-    const float h00 = (float)h0[0] * X.hf_vs, h01 = (float)h0[1] * X.hf_vs;
-    const float h10 = (float)h0[X.hf_cols] * X.hf_vs, h11 = (float)h0[X.hf_cols + 1] * X.hf_vs;
-    float du, dv;
-    if (fu >= fv) { du = h10 - h00; dv = h11 - h10; }
-    else { du = h11 - h01; dv = h01 - h00; }
-    return h00 + fu * du + fv * dv;
-}
 __device__ __forceinline__ const TerrainTail& terrain_tail(const lgs_task_params& T) {
     return *reinterpret_cast<const TerrainTail*>(&T + 1);
 }
@@ -2122,8 +2126,8 @@ __device__ __forceinline__ void height_scan(const TerrainTail& sp, const lgs_tas
 }
 
 // ground_relative_heights: what the base_height and feet_swing_height terms read, into
-// misc[16] (the mean of root_z - measured_heights over the scan) and misc[17 + f] (the ground
-// under foot f: terrain_sample's triangle).  The mean's order is fixed and does not depend on
+// misc[MI_CLEARANCE] (the mean of root_z - measured_heights over the scan) and
+// misc[MI_FOOT_GROUND + f] (the ground under foot f: terrain_sample's triangle).  The mean's order is fixed and does not depend on
 // the envs per wave: partial j < 32 adds its points k = j, j + 32, ... in rising k, the
 // partials are added j = 0..31, the total is divided by P.  The heights are read back from
 // the env buffer (after a barrier), so the split step's second launch takes the same path.
@@ -2141,8 +2145,9 @@ __device__ __forceinline__ void ground_heights(Smem<D, B, ROWS>& s, const lgs_ta
     float tot = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) tot += bc<EPW>(part, j);
-    if (lane == 0) s.u.post.misc[16] = tot / (float)P;
-    if (rbs && lane < T.num_feet) s.u.post.misc[17 + lane] = tail_ground(X, rbs[13 * in.fb], rbs[13 * in.fb + 1]);
+    if (lane == 0) s.u.post.misc[MI_CLEARANCE] = tot / (float)P;
+    if (rbs && lane < T.num_feet)  // (the block's copy of the map)
+        s.u.post.misc[MI_FOOT_GROUND + lane] = terrain_sample<false>(X, rbs[13 * in.fb], rbs[13 * in.fb + 1], nullptr);
 }
 
 // post_physics parts: everything, only up to the rewards (lgs_post_physics_rewards), or
@@ -2151,6 +2156,22 @@ __device__ __forceinline__ void ground_heights(Smem<D, B, ROWS>& s, const lgs_ta
 // commands / gait phase (lgs_post_physics_prepare), then termination and the rewards on
 // what the env buffers hold after a task's Python callback (lgs_post_physics_term_rewards)
 enum { PART_ALL = 0, PART_REWARDS = 1, PART_FINISH = 2, PART_PREPARE = 3, PART_TERM_REWARDS = 4 };
+
+// What an earlier part of the split step left in the env buffers (the base-frame state, the
+// gait phase) into misc, with the commands.  ENV_CMD: the env buffer's commands; else the ones
+// fetched with the state (s.pre.cmd: a Python callback ran in between).  One lane.
+template <bool ENV_CMD, int D, int B, int ROWS>
+__device__ __forceinline__ void misc_from_env(Smem<D, B, ROWS>& s, const lgs_env_buffers& E, int e) {
+    for (int i = 0; i < 3; ++i) {
+        s.u.post.misc[MI_LIN_VEL + i] = E.base_lin_vel[3 * e + i];
+        s.u.post.misc[MI_ANG_VEL + i] = E.base_ang_vel[3 * e + i];
+        s.u.post.misc[MI_GRAVITY + i] = E.projected_gravity[3 * e + i];
+    }
+    s.u.post.misc[MI_PHASE] = E.phase ? E.phase[e] : 0.f;
+    s.u.post.misc[MI_LEG_PHASE] = E.leg_phase ? E.leg_phase[2 * e] : 0.f;
+    s.u.post.misc[MI_LEG_PHASE + 1] = E.leg_phase ? E.leg_phase[2 * e + 1] : 0.f;
+    for (int i = 0; i < 4; ++i) s.u.post.misc[MI_CMD + i] = ENV_CMD ? E.commands[4 * e + i] : s.pre.cmd[i];
+}
 
 template <int D, int B, int ROWS, int EPW, bool PAD = false>
 __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& T, const lgs_env_buffers& E,
@@ -2172,15 +2193,7 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
             } else if (fabsf(E.rpy[3 * e + 1]) > 1.0f || fabsf(E.rpy[3 * e]) > 0.8f) reset = 1;
             const int timeout = (float)ep > T.max_episode_length;
             reset |= timeout;
-            for (int i = 0; i < 3; ++i) {
-                s.u.post.misc[i] = E.base_lin_vel[3 * e + i];
-                s.u.post.misc[3 + i] = E.base_ang_vel[3 * e + i];
-                s.u.post.misc[6 + i] = E.projected_gravity[3 * e + i];
-            }
-            s.u.post.misc[9] = E.phase ? E.phase[e] : 0.f;
-            s.u.post.misc[10] = E.leg_phase ? E.leg_phase[2 * e] : 0.f;
-            s.u.post.misc[11] = E.leg_phase ? E.leg_phase[2 * e + 1] : 0.f;
-            for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = s.pre.cmd[i];
+            misc_from_env<false>(s, E, e);
             s.flags[0] = reset;
             s.flags[1] = timeout;
         }
@@ -2199,7 +2212,7 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
             quat_rotate_inverse(qt, v, w);
             float* dst = (lane == 0 ? E.base_lin_vel : lane == 1 ? E.base_ang_vel : E.projected_gravity) + 3 * e;
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { dst[i] = w[i]; s.u.post.misc[3 * lane + i] = w[i]; }
+            for (int i = 0; i < 3; ++i) { dst[i] = w[i]; s.u.post.misc[MI_LIN_VEL + 3 * lane + i] = w[i]; }
             // termination mode 1: the gravity lane decides "fallen" (go2_handstand_env.py:211-212)
             term = T.termination_mode == 1 && lane == 2 && w[2] > -T.fallen_band && w[2] < T.fallen_band;
         } else if (lane < 7) {
@@ -2243,7 +2256,7 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
                     cmd[2] = clipf(0.5f * wv, -1.f, 1.f);
                     E.commands[4 * e + 2] = cmd[2];
                 }
-                for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = cmd[i];
+                for (int i = 0; i < 4; ++i) s.u.post.misc[MI_CMD + i] = cmd[i];
             }
         } else if (lane == 7) {
             E.episode_length[e] = ep;
@@ -2255,8 +2268,8 @@ __device__ void post_physics_scalar(Smem<D, B, ROWS>& s, const lgs_task_params& 
                 leg_phase[0] = phase;
                 leg_phase[1] = fmod_pos(phase + T.phase_offset, 1.0f);
             }
-            s.u.post.misc[9] = phase;
-            s.u.post.misc[10] = leg_phase[0]; s.u.post.misc[11] = leg_phase[1];
+            s.u.post.misc[MI_PHASE] = phase;
+            s.u.post.misc[MI_LEG_PHASE] = leg_phase[0]; s.u.post.misc[MI_LEG_PHASE + 1] = leg_phase[1];
             if (E.phase) E.phase[e] = phase;
             if (E.leg_phase) { E.leg_phase[2 * e] = leg_phase[0]; E.leg_phase[2 * e + 1] = leg_phase[1]; }
         } else if (lane - 8 < T.num_termination) {
@@ -2336,15 +2349,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
     } else if (lane == 0) {  // the first part's results: reset decision, base-frame state, commands
         s.flags[0] = E.reset[e];
         s.flags[1] = E.time_out[e];
-        for (int i = 0; i < 3; ++i) {
-            s.u.post.misc[i] = E.base_lin_vel[3 * e + i];
-            s.u.post.misc[3 + i] = E.base_ang_vel[3 * e + i];
-            s.u.post.misc[6 + i] = E.projected_gravity[3 * e + i];
-        }
-        s.u.post.misc[9] = E.phase ? E.phase[e] : 0.f;
-        s.u.post.misc[10] = E.leg_phase ? E.leg_phase[2 * e] : 0.f;
-        s.u.post.misc[11] = E.leg_phase ? E.leg_phase[2 * e + 1] : 0.f;
-        for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = E.commands[4 * e + i];
+        misc_from_env<true>(s, E, e);
     }
     __syncthreads();
     const int reset = s.flags[0];
@@ -2371,8 +2376,8 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
                 const float dx = s.root[0] - E.env_origins[3 * e], dy = s.root[1] - E.env_origins[3 * e + 1];
                 const float d2 = dx * dx + dy * dy;
                 // (lgs_reset_idx runs no callback: the commands are the env buffer's)
-                const float cx = reset_mode == RESET_IDS ? E.commands[4 * e] : s.u.post.misc[12];
-                const float cy = reset_mode == RESET_IDS ? E.commands[4 * e + 1] : s.u.post.misc[13];
+                const float cx = reset_mode == RESET_IDS ? E.commands[4 * e] : s.u.post.misc[MI_CMD];
+                const float cy = reset_mode == RESET_IDS ? E.commands[4 * e + 1] : s.u.post.misc[MI_CMD + 1];
                 const float half = 0.5f * T.max_episode_length_s;
                 const bool up = d2 > T.terrain_half_length_sq;
                 const bool down = !up && d2 < (cx * cx + cy * cy) * (half * half);
@@ -2422,7 +2427,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         if (lane == 0) {
             float* cmd = E.commands + 4 * e;
             resample_commands(T, cmd, seed, (uint32_t)e, step, LGS_STREAM_RESET_CMD);
-            for (int i = 0; i < 4; ++i) s.u.post.misc[12 + i] = cmd[i];  // (the observations' copy)
+            for (int i = 0; i < 4; ++i) s.u.post.misc[MI_CMD + i] = cmd[i];  // (the observations' copy)
             E.episode_length[e] = 0;
             s.pre.ep = 0;
         }
@@ -2447,23 +2452,23 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         for (int i = lane; i < K; i += WAVE / EPW) {
             float v;
             if (hand) {  // go2_handstand_env.py:140-154: [w*s, g, dq*s, qd*s, a, front flags, hind flags]
-                if (i < 3) v = mi[3 + i] * T.obs_scale_ang_vel;
-                else if (i < 6) v = mi[3 + i];
+                if (i < 3) v = mi[MI_ANG_VEL + i] * T.obs_scale_ang_vel;
+                else if (i < 6) v = mi[MI_GRAVITY + (i - 3)];
                 else if (i < 6 + Ad) v = (s.q[i - 6] - T.default_dof_pos[i - 6]) * T.obs_scale_dof_pos;
                 else if (i < 6 + 2 * Ad) v = s.qd[i - 6 - Ad] * T.obs_scale_dof_vel;
                 else if (i < 6 + 3 * Ad) v = act[i - 6 - 2 * Ad];
                 else  // the last substep's contact forces (a reset does not refresh them)
                     v = s.cf[T.feet_idx[i - 6 - 3 * Ad]][2] > T.contact_flag_threshold ? 1.f : 0.f;
             }
-            else if (i < 3) v = mi[i] * T.obs_scale_lin_vel;
-            else if (i < 6) v = mi[i] * T.obs_scale_ang_vel;
-            else if (i < 9) v = mi[i];
-            else if (i < 12) v = mi[12 + (i - 9)] * T.commands_scale[i - 9];
+            else if (i < 3) v = mi[MI_LIN_VEL + i] * T.obs_scale_lin_vel;
+            else if (i < 6) v = mi[MI_ANG_VEL + (i - 3)] * T.obs_scale_ang_vel;
+            else if (i < 9) v = mi[MI_GRAVITY + (i - 6)];
+            else if (i < 12) v = mi[MI_CMD + (i - 9)] * T.commands_scale[i - 9];
             else if (i < 12 + Ad) v = (s.q[i - 12] - T.default_dof_pos[i - 12]) * T.obs_scale_dof_pos;
             else if (i < 12 + 2 * Ad) v = s.qd[i - 12 - Ad] * T.obs_scale_dof_vel;
             else if (i < 12 + 3 * Ad) v = act[i - 12 - 2 * Ad];
             else {
-                float ph = 2.0f * 3.14159265358979323846f * mi[9];
+                float ph = 2.0f * 3.14159265358979323846f * mi[MI_PHASE];
                 float sp_, cp_;
                 lgs_sincosf(ph, &sp_, &cp_);
                 v = i == K - 2 ? sp_ : cp_;
@@ -2742,9 +2747,12 @@ __global__ void k_copy_rows(float* dst, const float* src, const int32_t* ids, in
 }
 
 // ------------------------------------------------------------ host side ----
+struct Inst;
+struct Kernels;
 struct lgs_sim {
     int N, B, D, P;
-    int Dt, Bt;  // the instantiation shape the model is padded to (>= D, B; see LGS_GENERIC_SHAPES)
+    const Inst* inst = nullptr;    // the table entry the model runs on (its shape >= D, B: the model is padded to it)
+    const Kernels* kern = nullptr; // its kernels for the model's DOF tree: chain-structured or dense
     int device;
     hipStream_t stream = nullptr;
     DevModel md{};
@@ -2771,17 +2779,16 @@ struct lgs_sim {
     lgs_height_obs hobs{};
     float hf_hs = 0.f;           // the heightfield's horizontal scale (TerrainTail::hf_hs)
     TerrainTail tail_host{};     // what the device block after task_dev holds (sync_terrain_tail)
-    int rows = 32;
-    int chain = 0;  // dof_chain_length of the model
-    int epw = 1;    // envs per wave of k_step (2 for the 32-row variant at even N)
+    int epw = 1;    // envs per wave of k_step (2 for a 32-row entry at even N)
     std::vector<std::string> body_names, dof_names;  // name queries (empty when not given)
 };
 
-// Compiled (dofs, max bodies, constraint-row capacity, chain length) variants.  The
-// row capacity sets the LDS footprint (Y, A): the 32-row variant is the Go2 one.  The
-// chain length CH is the sparsity the Cholesky exploits (l_nz); a tree that is not
-// D/CH equal chains hanging from the base takes the dense (CH = 0) variant.
-enum Variant { V_12_19, V_12_13_32, V_10_11_32, V_12_13, V_10_11, V_12_19_48, V_EXTRA, V_NONE };
+// ---- the compiled instantiations: one table, resolved once by lgs_create_sim ----
+// The robots of the registry, X(dofs, bodies, chain length): their kernels take the model's
+// sizes as compile-time bounds, so only the exact shape matches.  The chain length CH is the
+// sparsity the Cholesky exploits (l_nz); a tree that is not D/CH equal chains hanging from the
+// base takes the same shape's dense (CH = 0) kernels.
+#define LGS_ROBOT_SHAPES X(12, 13, 6) X(10, 11, 5) X(12, 19, 3)
 
 // Build-time instantiation hook for other robots: every X(D, B) listed here compiles the
 // 48-row, one-env-per-wave kernels (dense Cholesky) for models with exactly D DOFs and at
@@ -2803,159 +2810,73 @@ enum Variant { V_12_19, V_12_13_32, V_10_11_32, V_12_13, V_10_11, V_12_19_48, V_
 #ifndef LGS_GENERIC_SHAPES
 #define LGS_GENERIC_SHAPES X(16, 24) X(26, 32)
 #endif
-#define LGS_ALL_48_SHAPES LGS_EXTRA_SHAPES LGS_GENERIC_SHAPES
 
-// the instantiation shape (Dt, Bt) a model of D DOFs and B bodies is padded to among the
-// extra (exact D) and generic (padded D) shapes; false if none fits
-static bool extra_shape(int D, int B, int* Dt, int* Bt) {
-#define X(D_, B_) if (D == D_ && B <= B_) { *Dt = D_; *Bt = B_; return true; }
+// how an entry's shape (Dt, Bt) takes a model's (D, B)
+enum Fit {
+    FIT_EXACT,   // D == Dt, B == Bt
+    FIT_BODIES,  // D == Dt, B <= Bt: inert bodies appended (LGS_EXTRA_SHAPES)
+    FIT_DOFS     // D <= Dt, B + (Dt - D) <= Bt: inert DOFs, then bodies (LGS_GENERIC_SHAPES)
+};
+
+// one shape's kernels for one factorisation (chain-structured or dense)
+struct Kernels {
+    using Step = void (*)(DevModel, DevSim, DevState, const lgs_task_params*, lgs_env_buffers, int, uint32_t, int);
+    Step step;        // one env per wave
+    Step step_small;  // its 4 waves/SIMD build, for env counts within one round of waves (else null)
+    Step step2;       // two envs per wave (else null)
+    void (*simulate)(DevModel, DevSim, DevState, int);
+    void (*fk)(DevModel, DevState, int);
+    void (*reset_all)(DevModel, DevState, const lgs_task_params*, lgs_env_buffers, int, uint32_t, const uint8_t*);
+};
+// The builds of k_step an entry has.  EPW2 (the 32-row entries: the row capacity sets the LDS
+// footprint, Y and A): one and two envs per wave.  Else one env per wave: an exact shape at
+// the default waves/SIMD and at 4 (worth its spills while all envs fit one round of waves), a
+// padded one at 2 alone (the 29-row dense factorisation does not fit the 48-row default's 168
+// VGPRs).
+template <int D, int B, int ROWS, int CH, bool PAD, bool EPW2>
+static Kernels kernels_of() {
+    Kernels k{};
+    k.step = k_step<D, B, ROWS, CH, 1, PAD ? 2 : 0, PAD>;
+    if constexpr (EPW2) k.step2 = k_step<D, B, ROWS, CH, 2, 0, PAD>;
+    else if constexpr (!PAD) k.step_small = k_step<D, B, ROWS, CH, 1, 4, PAD>;
+    k.simulate = k_simulate<D, B, ROWS, CH, PAD>;
+    k.fk = k_fk<D, B, ROWS, CH, PAD>;
+    k.reset_all = k_reset_all<D, B, ROWS, CH, PAD>;
+    return k;
+}
+
+struct Inst {
+    int Dt, Bt;  // the shape
+    int rows;    // constraint-row capacity: 32 or 48
+    int chain;   // chain length of the structured Cholesky (0: the shape has the dense one alone)
+    Fit fit;
+    bool epw2;   // has a two-envs-per-wave k_step
+    Kernels chained, dense;  // (chain == 0: both the dense kernels)
+    bool takes(int D, int B) const {
+        return fit == FIT_DOFS ? D <= Dt && B + (Dt - D) <= Bt : D == Dt && (fit == FIT_BODIES ? B <= Bt : B == Bt);
+    }
+};
+template <int D, int B, int ROWS, int CH, Fit FIT, bool EPW2>
+static Inst inst_of() {
+    constexpr bool PAD = FIT != FIT_EXACT;
+    return {D, B, ROWS, CH, FIT, EPW2, kernels_of<D, B, ROWS, CH, PAD, EPW2>(), kernels_of<D, B, ROWS, 0, PAD, EPW2>()};
+}
+// In priority order: lgs_create_sim takes the first entry whose shape takes the model and
+// whose rows hold max_rows.
+static const Inst g_insts[] = {
+#define X(D_, B_, CH_) inst_of<D_, B_, 32, CH_, FIT_EXACT, true>(),
+    LGS_ROBOT_SHAPES
+#undef X
+#define X(D_, B_, CH_) inst_of<D_, B_, 48, CH_, FIT_EXACT, false>(),
+    LGS_ROBOT_SHAPES
+#undef X
+#define X(D_, B_) inst_of<D_, B_, 48, 0, FIT_BODIES, false>(),
     LGS_EXTRA_SHAPES
 #undef X
-#define X(D_, B_) if (D <= D_ && B + (D_ - D) <= B_) { *Dt = D_; *Bt = B_; return true; }
+#define X(D_, B_) inst_of<D_, B_, 48, 0, FIT_DOFS, false>(),
     LGS_GENERIC_SHAPES
 #undef X
-    return false;
-}
-static bool extra_shape(const lgs_sim* s) {
-    int dt, bt;
-    return extra_shape(s->D, s->B, &dt, &bt);
-}
-
-static Variant pick(const lgs_sim* s) {
-    // 32-row humanoid variants (8 contacts): two envs per wave, as Go2
-    // (exact shapes only: these kernels take the model's sizes as compile-time bounds)
-    if (s->D == 12 && s->B == 13 && s->rows <= 32) return V_12_13_32;
-    if (s->D == 10 && s->B == 11 && s->rows <= 32) return V_10_11_32;
-    if (s->D == 12 && s->B == 19 && s->rows <= 32) return V_12_19;
-    if (s->D == 12 && s->B == 13) return V_12_13;
-    if (s->D == 12 && s->B == 19) return V_12_19_48;
-    if (s->D == 10 && s->B == 11) return V_10_11;
-    if (extra_shape(s)) return V_EXTRA;
-    return V_NONE;
-}
-static void variant_shape(const lgs_sim* s, Variant v, int* Dt, int* Bt) {
-    switch (v) {
-    case V_12_19: case V_12_19_48: *Dt = 12; *Bt = 19; break;
-    case V_12_13_32: case V_12_13: *Dt = 12; *Bt = 13; break;
-    case V_10_11_32: case V_10_11: *Dt = 10; *Bt = 11; break;
-    default: if (!extra_shape(s->D, s->B, Dt, Bt)) { *Dt = s->D; *Bt = s->B; }
-    }
-}
-static int variant_rows(Variant v) { return (v == V_12_19 || v == V_12_13_32 || v == V_10_11_32) ? 32 : 48; }  // (V_EXTRA: 48)
-static int variant_chain(Variant v) {
-    return (v == V_12_13 || v == V_12_13_32) ? 6 : ((v == V_10_11 || v == V_10_11_32) ? 5 : 3);
-}
-
-#define LGS_LAUNCH(sim, KERNEL, D_, B_, R_, ...)                                                         \
-    do {                                                                                                 \
-        if ((sim)->chain == variant_chain(pick(sim)))                                                    \
-            hipLaunchKernelGGL((KERNEL<D_, B_, R_, (D_ == 10 ? 5 : (B_ == 13 ? 6 : 3))>), dim3((sim)->N), \
-                               dim3(WAVE), 0, (sim)->stream, __VA_ARGS__);                               \
-        else                                                                                             \
-            hipLaunchKernelGGL((KERNEL<D_, B_, R_, 0>), dim3((sim)->N), dim3(WAVE), 0, (sim)->stream,    \
-                               __VA_ARGS__);                                                             \
-    } while (0)
-// k_step with EPW envs per wave (grid N / EPW)
-#define LGS_LAUNCH_EPW(sim, KERNEL, D_, B_, R_, EPW_, ...)                                                 \
-    do {                                                                                                  \
-        if ((sim)->chain == variant_chain(pick(sim)))                                                     \
-            hipLaunchKernelGGL((KERNEL<D_, B_, R_, (D_ == 10 ? 5 : (B_ == 13 ? 6 : 3)), EPW_>),            \
-                               dim3((sim)->N / EPW_), dim3(WAVE), 0, (sim)->stream, __VA_ARGS__);         \
-        else                                                                                              \
-            hipLaunchKernelGGL((KERNEL<D_, B_, R_, 0, EPW_>), dim3((sim)->N / EPW_), dim3(WAVE), 0,        \
-                               (sim)->stream, __VA_ARGS__);                                               \
-    } while (0)
-// the 48-row variants: 4 waves/SIMD when all envs fit one round of them, else the default
-#define LGS_LAUNCH_48W(sim, KERNEL, D_, B_, WPE_, ...)                                                    \
-    do {                                                                                                  \
-        if ((sim)->chain == variant_chain(pick(sim)))                                                     \
-            hipLaunchKernelGGL((KERNEL<D_, B_, 48, (D_ == 10 ? 5 : (B_ == 13 ? 6 : 3)), 1, WPE_>),        \
-                               dim3((sim)->N), dim3(WAVE), 0, (sim)->stream, __VA_ARGS__);                \
-        else                                                                                              \
-            hipLaunchKernelGGL((KERNEL<D_, B_, 48, 0, 1, WPE_>), dim3((sim)->N), dim3(WAVE), 0,           \
-                               (sim)->stream, __VA_ARGS__);                                               \
-    } while (0)
-#define LGS_LAUNCH_48(sim, KERNEL, D_, B_, ...)                                                           \
-    do {                                                                                                  \
-        if ((sim)->N <= 4 * 1024) LGS_LAUNCH_48W(sim, KERNEL, D_, B_, 4, __VA_ARGS__);                    \
-        else LGS_LAUNCH_48W(sim, KERNEL, D_, B_, 0, __VA_ARGS__);                                         \
-    } while (0)
-// the extra shapes' launches (one env per wave, 48 rows, CH = 0)
-template <int D, int B>
-static void ex_step(const lgs_sim* s, DevModel md, DevSim sp, DevState st, const lgs_task_params* tp,
-                    lgs_env_buffers E, int N, uint32_t step, int mode) {
-    // (2 waves/SIMD: the 29-row dense factorisation does not fit the 48-row default's 168 VGPRs)
-    hipLaunchKernelGGL((k_step<D, B, 48, 0, 1, 2, true>), dim3(N), dim3(WAVE), 0, s->stream, md, sp, st, tp, E, N, step, mode);
-}
-template <int D, int B>
-static void ex_simulate(const lgs_sim* s, DevModel md, DevSim sp, DevState st, int N) {
-    hipLaunchKernelGGL((k_simulate<D, B, 48, 0, true>), dim3(N), dim3(WAVE), 0, s->stream, md, sp, st, N);
-}
-template <int D, int B>
-static void ex_fk(const lgs_sim* s, DevModel md, DevState st, int N) {
-    hipLaunchKernelGGL((k_fk<D, B, 48, 0, true>), dim3(N), dim3(WAVE), 0, s->stream, md, st, N);
-}
-template <int D, int B>
-static void ex_reset(const lgs_sim* s, DevModel md, DevState st, const lgs_task_params* tp, lgs_env_buffers E, int N,
-                     uint32_t step, const uint8_t* mask) {
-    hipLaunchKernelGGL((k_reset_all<D, B, 48, 0, true>), dim3(N), dim3(WAVE), 0, s->stream, md, st, tp, E, N, step, mask);
-}
-static int extra_step(const lgs_sim* s, DevModel md, DevSim sp, DevState st, const lgs_task_params* tp,
-                      lgs_env_buffers E, int N, uint32_t step, int mode) {
-#define X(D_, B_) if (s->Dt == D_ && s->Bt == B_) { ex_step<D_, B_>(s, md, sp, st, tp, E, N, step, mode); return LGS_OK; }
-    LGS_ALL_48_SHAPES
-#undef X
-    return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");
-}
-static int extra_simulate(const lgs_sim* s, DevModel md, DevSim sp, DevState st, int N) {
-#define X(D_, B_) if (s->Dt == D_ && s->Bt == B_) { ex_simulate<D_, B_>(s, md, sp, st, N); return LGS_OK; }
-    LGS_ALL_48_SHAPES
-#undef X
-    return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");
-}
-static int extra_fk(const lgs_sim* s, DevModel md, DevState st, int N) {
-#define X(D_, B_) if (s->Dt == D_ && s->Bt == B_) { ex_fk<D_, B_>(s, md, st, N); return LGS_OK; }
-    LGS_ALL_48_SHAPES
-#undef X
-    return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");
-}
-static int extra_reset(const lgs_sim* s, DevModel md, DevState st, const lgs_task_params* tp, lgs_env_buffers E,
-                       int N, uint32_t step, const uint8_t* mask) {
-#define X(D_, B_) if (s->Dt == D_ && s->Bt == B_) { ex_reset<D_, B_>(s, md, st, tp, E, N, step, mask); return LGS_OK; }
-    LGS_ALL_48_SHAPES
-#undef X
-    return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");
-}
-
-#define LGS_DISPATCH_STEP(sim, KERNEL, ...)                                                               \
-    switch (pick(sim)) {                                                                                  \
-    case V_12_19:                                                                                         \
-        if ((sim)->epw == 2) LGS_LAUNCH_EPW(sim, KERNEL, 12, 19, 32, 2, __VA_ARGS__);                     \
-        else LGS_LAUNCH_EPW(sim, KERNEL, 12, 19, 32, 1, __VA_ARGS__);                                     \
-        break;                                                                                            \
-    case V_12_13_32:                                                                                      \
-        if ((sim)->epw == 2) LGS_LAUNCH_EPW(sim, KERNEL, 12, 13, 32, 2, __VA_ARGS__);                     \
-        else LGS_LAUNCH_EPW(sim, KERNEL, 12, 13, 32, 1, __VA_ARGS__);                                     \
-        break;                                                                                            \
-    case V_10_11_32:                                                                                      \
-        if ((sim)->epw == 2) LGS_LAUNCH_EPW(sim, KERNEL, 10, 11, 32, 2, __VA_ARGS__);                     \
-        else LGS_LAUNCH_EPW(sim, KERNEL, 10, 11, 32, 1, __VA_ARGS__);                                     \
-        break;                                                                                            \
-    case V_12_13: LGS_LAUNCH_48(sim, KERNEL, 12, 13, __VA_ARGS__); break;                                 \
-    case V_10_11: LGS_LAUNCH_48(sim, KERNEL, 10, 11, __VA_ARGS__); break;                                 \
-    case V_12_19_48: LGS_LAUNCH_48(sim, KERNEL, 12, 19, __VA_ARGS__); break;                              \
-    default: return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");                                 \
-    }
-#define LGS_DISPATCH(sim, KERNEL, ...)                                                                    \
-    switch (pick(sim)) {                                                                                  \
-    case V_12_19: LGS_LAUNCH(sim, KERNEL, 12, 19, 32, __VA_ARGS__); break;                                \
-    case V_12_13_32: LGS_LAUNCH(sim, KERNEL, 12, 13, 32, __VA_ARGS__); break;                             \
-    case V_10_11_32: LGS_LAUNCH(sim, KERNEL, 10, 11, 32, __VA_ARGS__); break;                             \
-    case V_12_13: LGS_LAUNCH(sim, KERNEL, 12, 13, 48, __VA_ARGS__); break;                                \
-    case V_10_11: LGS_LAUNCH(sim, KERNEL, 10, 11, 48, __VA_ARGS__); break;                                \
-    case V_12_19_48: LGS_LAUNCH(sim, KERNEL, 12, 19, 48, __VA_ARGS__); break;                             \
-    default: return set_err(LGS_ERR_ARG, "unsupported model size (D,B)");                                 \
-    }
+};
 
 // Chain length of the DOF tree: CH if the D DOFs are D/CH chains of CH joints, each
 // hanging from the base, in DFS order (DOF j's nearest moving ancestor is DOF j-1, or
@@ -3013,21 +2934,25 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
     HIP_TRY(hipSetDevice(device_id));
     lgs_sim* s = new lgs_sim();
     s->N = num_envs; s->B = m->num_bodies; s->D = m->num_dofs; s->P = m->num_points; s->device = device_id;
-    s->rows = p->max_rows;
-    s->chain = dof_chain_length(m);
-    // two envs per wave for the 32-row variant at an even env count (LGS_ENVS_PER_WAVE=1: one)
-    {
-        const char* ev = getenv("LGS_ENVS_PER_WAVE");
-        const bool one = ev && atoi(ev) == 1;
-        const Variant v = pick(s);
-        s->epw = (!one && num_envs % 2 == 0 && (v == V_12_19 || v == V_12_13_32 || v == V_10_11_32)) ? 2 : 1;
+    // (rows beyond every capacity: the last entry that takes the shape words the refusal below)
+    for (const Inst& i : g_insts) {
+        if (!i.takes(s->D, s->B)) continue;
+        s->inst = &i;
+        if (p->max_rows <= i.rows) break;
     }
-    if (pick(s) == V_NONE) {
+    if (!s->inst) {
         delete s;
         return set_err(LGS_ERR_ARG, "lgs_create_sim: no kernel instantiation for this (dofs, bodies)");
     }
+    s->kern = (s->inst->chain && dof_chain_length(m) == s->inst->chain) ? &s->inst->chained : &s->inst->dense;
+    // two envs per wave for a 32-row entry at an even env count (LGS_ENVS_PER_WAVE=1: one)
     {
-        const int cap = variant_rows(pick(s));
+        const char* ev = getenv("LGS_ENVS_PER_WAVE");
+        const bool one = ev && atoi(ev) == 1;
+        s->epw = (!one && num_envs % 2 == 0 && s->inst->epw2) ? 2 : 1;
+    }
+    {
+        const int cap = s->inst->rows;
         // contact c occupies rows 3c..3c+2 (c < cap/4), limit rows the tail block
         const int cm = cap / 4, lm = cap - 3 * cm;
         if (p->max_rows > cap || p->max_rows < 3 * p->max_contacts || p->max_contacts < 0 || p->max_contacts > cm ||
@@ -3039,7 +2964,6 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
         }
     }
     const int B = s->B, D = s->D, P = s->P;
-    variant_shape(s, pick(s), &s->Dt, &s->Bt);
     if (m->body_names)
         for (int b = 0; b < B; ++b) s->body_names.emplace_back(m->body_names[b] ? m->body_names[b] : "");
     if (m->dof_names)
@@ -3081,7 +3005,7 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
     // the model padded to the instantiation shape (Dt, Bt): DOF D + k on body B + k, a
     // massless body hinged to the base about z (M_jj = 1 in the kernel, no limits); then
     // fixed massless bodies on the base; the base's subtree covers them all
-    const int Dt = s->Dt, Bt = s->Bt;
+    const int Dt = s->inst->Dt, Bt = s->inst->Bt;
     std::vector<int> parent(m->parent, m->parent + B), dofv(m->dof, m->dof + B), se(m->subtree_end, m->subtree_end + B);
     std::vector<int> depth(m->depth, m->depth + B), chain(m->chain, m->chain + (size_t)B * LGS_MAX_DEPTH);
     std::vector<float> jr(m->joint_rot, m->joint_rot + 9 * B), jp(m->joint_pos, m->joint_pos + 3 * B);
@@ -3299,26 +3223,14 @@ LGS_API int lgs_set_dof_actuation_force(lgs_sim* s, const float* tau) {
 LGS_API int lgs_simulate(lgs_sim* s) {
     if (!s || !s->root) return set_err(LGS_ERR_STATE, "lgs_simulate: state not bound");
     if (!s->torques) return set_err(LGS_ERR_STATE, "lgs_simulate: no actuation force set");
-    DevState st = state_of(s);
-    if (pick(s) == V_EXTRA) {
-        const int rc = extra_simulate(s, s->md, s->sp, st, s->N);
-        if (rc != LGS_OK) return rc;
-    } else {
-        LGS_DISPATCH(s, k_simulate, s->md, s->sp, st, s->N);
-    }
+    hipLaunchKernelGGL(s->kern->simulate, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, s->sp, state_of(s), s->N);
     HIP_TRY(hipGetLastError());
     return LGS_OK;
 }
 
 LGS_API int lgs_forward_kinematics(lgs_sim* s) {
     if (!s || !s->root) return set_err(LGS_ERR_STATE, "state not bound");
-    DevState st = state_of(s);
-    if (pick(s) == V_EXTRA) {
-        const int rc = extra_fk(s, s->md, st, s->N);
-        if (rc != LGS_OK) return rc;
-    } else {
-        LGS_DISPATCH(s, k_fk, s->md, st, s->N);
-    }
+    hipLaunchKernelGGL(s->kern->fk, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, state_of(s), s->N);
     HIP_TRY(hipGetLastError());
     return LGS_OK;
 }
@@ -3469,13 +3381,11 @@ static int launch_step(lgs_sim* s, const lgs_env_buffers* env, int64_t step_coun
     if (!s || !env) return set_err(LGS_ERR_ARG, std::string(what) + ": null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, std::string(what) + ": state not bound or task not set");
     if (const int rc = check_terrain_buffers(s, env, what)) return rc;
-    DevState st = state_of(s);
-    if (pick(s) == V_EXTRA) {
-        const int rc = extra_step(s, s->md, s->sp, st, s->task_dev, *env, s->N, (uint32_t)step_counter, mode);
-        if (rc != LGS_OK) return rc;
-    } else {
-        LGS_DISPATCH_STEP(s, k_step, s->md, s->sp, st, s->task_dev, *env, s->N, (uint32_t)step_counter, mode);
-    }
+    // (an entry's 4 waves/SIMD build: while all envs fit one round of waves)
+    const Kernels& k = *s->kern;
+    const Kernels::Step step = s->epw == 2 ? k.step2 : (k.step_small && s->N <= 4096 ? k.step_small : k.step);
+    hipLaunchKernelGGL(step, dim3(s->N / s->epw), dim3(WAVE), 0, s->stream, s->md, s->sp, state_of(s),
+                       s->task_dev, *env, s->N, (uint32_t)step_counter, mode);
     HIP_TRY(hipGetLastError());
     if (extras && (mode == MODE_STEP || mode == MODE_POST || mode == MODE_POST_FINISH)) {  // extras, episode_acc zeroed, counter advanced
         hipLaunchKernelGGL(k_step_extras, dim3(1), dim3(1024), 0, s->stream, *env, s->task_dev, s->N, 1,
@@ -3537,13 +3447,8 @@ LGS_API int lgs_reset_all(lgs_sim* s, const lgs_env_buffers* env, int64_t step_c
     if (!s || !env) return set_err(LGS_ERR_ARG, "null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_all: state not bound or task not set");
     if (const int rc = check_obs_width(s, "lgs_reset_all")) return rc;
-    DevState st = state_of(s);
-    if (pick(s) == V_EXTRA) {
-        const int rc = extra_reset(s, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, nullptr);
-        if (rc != LGS_OK) return rc;
-    } else {
-        LGS_DISPATCH(s, k_reset_all, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, (const uint8_t*)nullptr);
-    }
+    hipLaunchKernelGGL(s->kern->reset_all, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, state_of(s),
+                       s->task_dev, *env, s->N, (uint32_t)step_counter, nullptr);
     HIP_TRY(hipGetLastError());
     return LGS_OK;
 }
@@ -3552,13 +3457,8 @@ LGS_API int lgs_reset_idx(lgs_sim* s, const lgs_env_buffers* env, const uint8_t*
     if (!s || !env || !env_mask) return set_err(LGS_ERR_ARG, "lgs_reset_idx: null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_idx: state not bound or task not set");
     if (const int rc = check_terrain_buffers(s, env, "lgs_reset_idx")) return rc;
-    DevState st = state_of(s);
-    if (pick(s) == V_EXTRA) {
-        const int rc = extra_reset(s, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, env_mask);
-        if (rc != LGS_OK) return rc;
-    } else {
-        LGS_DISPATCH(s, k_reset_all, s->md, st, s->task_dev, *env, s->N, (uint32_t)step_counter, env_mask);
-    }
+    hipLaunchKernelGGL(s->kern->reset_all, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, state_of(s),
+                       s->task_dev, *env, s->N, (uint32_t)step_counter, env_mask);
     HIP_TRY(hipGetLastError());
     // extras["episode"] over the reset envs and extras["time_outs"]; no step-counter advance
     hipLaunchKernelGGL(k_step_extras, dim3(1), dim3(1024), 0, s->stream, *env, s->task_dev, s->N, 0,
@@ -3617,16 +3517,15 @@ LGS_API int32_t lgs_find_dof(lgs_sim* s, const char* name) { return s ? find_nam
 
 LGS_API int lgs_get_instantiation(lgs_sim* s, int32_t* dofs, int32_t* bodies, int32_t* rows) {
     if (!s) return set_err(LGS_ERR_ARG, "null argument");
-    if (dofs) *dofs = s->Dt;
-    if (bodies) *bodies = s->Bt;
-    if (rows) *rows = variant_rows(pick(s));
+    if (dofs) *dofs = s->inst->Dt;
+    if (bodies) *bodies = s->inst->Bt;
+    if (rows) *rows = s->inst->rows;
     return LGS_OK;
 }
 
 LGS_API int lgs_get_factor_chain(lgs_sim* s, int32_t* chain) {
     if (!s || !chain) return set_err(LGS_ERR_ARG, "null argument");
-    const Variant v = pick(s);
-    *chain = (v != V_EXTRA && v != V_NONE && s->chain == variant_chain(v)) ? variant_chain(v) : 0;
+    *chain = s->kern == &s->inst->chained ? s->inst->chain : 0;
     return LGS_OK;
 }
 

@@ -262,12 +262,16 @@ class Sim:
               "lgs_get_contact_stats")
         return {"bodies": int(out[0]), "self": int(out[1]), "limits": int(out[2])}
 
+    def instantiation(self):
+        """(DOFs, bodies, constraint-row capacity) of the compiled kernels the sim runs on."""
+        d, b, r = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.lib, self.lib.lgs_get_instantiation(self.handle, C.byref(d), C.byref(b), C.byref(r)),
+              "lgs_get_instantiation")
+        return d.value, b.value, r.value
+
     def padded_shape(self):
         """(DOFs, bodies) of the compiled kernel the sim runs on (the model padded to it)."""
-        d, b = C.c_int32(), C.c_int32()
-        check(self.lib, self.lib.lgs_get_instantiation(self.handle, C.byref(d), C.byref(b), None),
-              "lgs_get_instantiation")
-        return d.value, b.value
+        return self.instantiation()[:2]
 
     def factor_chain(self):
         """The chain length the kernel's Cholesky eliminates level by level (0: index order);

@@ -24,6 +24,7 @@ from rsl_rl.modules import ActorCritic
 from rsl_rl.modules import mfma_mlp
 from rsl_rl.storage import RolloutStorage
 from rsl_rl.storage.rollout_storage import minibatch_permutation
+from rsl_rl.utils import capture_without_gc
 
 
 def _dist_world():
@@ -532,7 +533,7 @@ class PPO:
         runs the same collectives eagerly.  Returns True when the graph is usable."""
         err = None
         try:
-            with torch.cuda.graph(graph, stream=stream):
+            with capture_without_gc(), torch.cuda.graph(graph, stream=stream):
                 body()
         except RuntimeError as e:
             err = e

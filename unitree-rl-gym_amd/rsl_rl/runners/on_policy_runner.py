@@ -13,6 +13,7 @@ import torch.distributed as dist
 from rsl_rl.algorithms import PPO  # noqa: F401  (eval'd by name)
 from rsl_rl.env import VecEnv
 from rsl_rl.modules import ActorCritic, ActorCriticRecurrent  # noqa: F401  (eval'd by name)
+from rsl_rl.utils import capture_without_gc
 
 
 class _JsonlWriter:
@@ -70,7 +71,7 @@ class _RolloutGraph:
         self.graph = torch.cuda.CUDAGraph()
         # captured outside inference mode: the graph's RNG offset tensors must stay
         # ordinary tensors (replays update them in place)
-        with torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(self.graph):
+        with capture_without_gc(), torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(self.graph):
             for t in range(T):
                 obs, critic_obs, rewards, dones, infos = runner._collect_step(obs, critic_obs)
                 if self.log:

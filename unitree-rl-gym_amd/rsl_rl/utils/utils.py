@@ -1,4 +1,24 @@
+import contextlib
+import gc
+
 import torch
+
+
+@contextlib.contextmanager
+def capture_without_gc():
+    """Around a stream capture (torch.cuda.graph).  A cyclic-garbage collection that lands
+    inside a capture runs whatever finalizers are due there -- an earlier env's Sim
+    (lgs_destroy_sim: hipFree), an earlier runner's graphs -- and their HIP calls are illegal
+    while the device captures: the process aborts.  So collect first, and keep the collector
+    off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def split_and_pad_trajectories(tensor, dones):
