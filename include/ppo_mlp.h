@@ -539,4 +539,39 @@ PMLP_API int pmlp_lstm_bwd_dw_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs
  * or neither); x, w_ih, b_ih, b_hh, w_hh as above; the other fields are ignored.          */
 PMLP_API int pmlp_lstm_step_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t B, int32_t H, void* stream);
 
+/* ---- wide inputs: a hidden-64 memory whose input is 65 .. pmlp_lstm_wide_max_input() (384)
+ * columns, e.g. an observation row with the height scan.  W_ih no longer fits the sequence
+ * kernel's lanes, so the input projection runs first as one split-bf16 matrix-core product
+ * over all T*B rows, gx = x W_ih^T + b_ih + b_hh, and the sequence kernel starts each step's
+ * accumulators from the env's gx row (the arithmetic of pmlp_lstm_fwd_mfma otherwise).
+ *   forward:  x [T,B,I] (rows of I floats: 4-byte alignment is all they have), w_ih, b_ih,
+ *             b_hh, w_hh, h0, c0 (NULL: zeros) -> gx [T,B,256], h_out, c_out [T,B,64],
+ *             gact [T,B,256], hp [T,B,65] = [h_prev | 1] (the backward's operand)
+ *   backward: w_hh, c0, c_out, gact, hp, dh_out, x -> dgx [T,B,256],
+ *             slab    [pmlp_lstm_bwd_dw_blocks(B)][dW_hh (256 x 64) | db (256)],
+ *             slab_ih [pmlp_lstm_wide_dw_blocks(T, B)][dW_ih (256 x I)]
+ *             (partial sums, torch row order; pmlp_reduce_slabs adds the rows up)
+ *   step:     one rollout step (T = 1) with h = h_out, c = c_out [B,64] updated in place,
+ *             gx [B,256] scratch, h_save / c_save optional (both or neither): the same two
+ *             kernels as the forward, so the step's h is the forward's h_out[0] bit for bit.
+ * Each entry takes 1..2 jobs (side by side in the grid), H = 64 and 65 <= I <= 384; every
+ * check runs before the first launch (text in pmlp_lstm_last_error).                       */
+typedef struct pmlp_lstm_wide_job {
+    int32_t I;
+    const float *x, *w_ih, *b_ih, *b_hh, *w_hh;
+    const float *h0, *c0;
+    float *h_out, *c_out, *gact, *gx, *hp;
+    const float* dh_out;
+    float *dgx, *slab, *slab_ih;
+    float *h_save, *c_save;
+} pmlp_lstm_wide_job;
+PMLP_API int32_t pmlp_lstm_wide_max_input(void);
+PMLP_API int32_t pmlp_lstm_wide_dw_blocks(int32_t T, int32_t B);
+PMLP_API int pmlp_lstm_fwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t T, int32_t B, int32_t H,
+                                     const uint8_t* reset, void* stream);
+PMLP_API int pmlp_lstm_bwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t T, int32_t B, int32_t H,
+                                     const uint8_t* reset, void* stream);
+PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t B, int32_t H,
+                                      void* stream);
+
 #endif

@@ -875,6 +875,418 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
     }
 }
 
+// -------------------------------------------------------------- wide inputs --
+// Inputs of 65 .. 384 columns (an observation row with the height scan): W_ih no longer fits
+// the lanes (k_lstm_fwd_mfma8's wf would be ~160 VGPRs at I = 240) nor LDS (245 KB as bf16
+// hi + lo), and the input projection has no recurrence in it, so it runs beforehand as one
+// product over all T B rows (k_lstm_proj_wide -> gx); the sequence kernel (k_lstm_fwd_gx8)
+// starts each step's accumulators from the env's gx row instead of the bias and keeps only
+// the 64 h columns as K.  The backward is k_lstm_bwd_mfma<3, true> on the x-less operand
+// [h_prev | 1] (I = 0, RL = 65: dW_hh and db in its slabs) writing dgx, and dW_ih = dGx^T X
+// is one more product over the rows (k_lstm_dwih_wide).  Every product is the split-bf16
+// form above (hi.hi + hi.lo + lo.hi, fp32 accumulation).
+constexpr int WI_MIN = MKX + 1, WI_MAX = 384;  // input widths of the wide form
+constexpr int PM = 64, PK = 32;                // projection: rows per workgroup, k-chunk
+constexpr int PLD = PK + 8;                    // LDS row stride of a k-chunk (bf16): 80 B
+constexpr int MLDH = MH + 8;                   // LDS row stride of h (bf16): 144 B
+constexpr int WDR = 512, WDC = 128;            // dW_ih: rows and x columns per workgroup
+
+struct WProjArgs {
+    int M, I;
+    const float *x, *wih, *bih, *bhh;
+    float* gx;
+};
+struct WProjBatch { WProjArgs m[2]; };  // as MFwdBatch
+
+// gx [M, 256] = x [M, I] . W_ih^T + (b_ih + b_hh): a workgroup of 4 waves owns PM rows and all
+// 256 gate columns (wave w: columns 64w .. 64w + 63 as 2 x 2 tiles of v_mfma_f32_32x32x16_bf16,
+// the accumulators starting from the fp32 bias); x and W_ih go through LDS one PK-deep k-chunk
+// at a time, split into bf16 (hi, lo) on the way, the next chunk's loads in flight behind the
+// products.  x rows start wherever I floats put them (237: 4-byte aligned only), so every
+// global load is one element, coalesced along k; the k tail past I is zero.
+__global__ __launch_bounds__(256) void k_lstm_proj_wide(WProjBatch ab) {
+    const WProjArgs a = ab.m[blockIdx.y];
+    const int M = a.M, I = a.I, r0 = blockIdx.x * PM;
+    if (r0 >= M) return;  // (whole workgroup)
+    __shared__ __attribute__((aligned(16))) mbf16 Xs[2][PM * PLD];
+    __shared__ __attribute__((aligned(16))) mbf16 Ws[2][MG * PLD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l32 = lane & 31, lh = lane >> 5;
+    const int kk = tid & 31, rr = tid >> 5;  // staging: column kk of rows rr, rr + 8, ..
+    float xv[PM / 8], wv[MG / 8];
+    // unconditional loads at clamped addresses, masked where stored (see k_lstm_fwd_mfma8)
+    auto load = [&](int k0) {
+        const int kc = min(k0 + kk, I - 1);
+#pragma unroll
+        for (int i = 0; i < PM / 8; ++i) xv[i] = a.x[(size_t)min(r0 + rr + 8 * i, M - 1) * I + kc];
+#pragma unroll
+        for (int i = 0; i < MG / 8; ++i) wv[i] = a.wih[(size_t)(rr + 8 * i) * I + kc];
+    };
+    auto store = [&](int k0) {
+        const bool in = k0 + kk < I;
+#pragma unroll
+        for (int i = 0; i < PM / 8; ++i) {
+            mbf16 hi, lo;
+            split_bf16(in ? xv[i] : 0.f, hi, lo);
+            Xs[0][(rr + 8 * i) * PLD + kk] = hi;
+            Xs[1][(rr + 8 * i) * PLD + kk] = lo;
+        }
+#pragma unroll
+        for (int i = 0; i < MG / 8; ++i) {
+            mbf16 hi, lo;
+            split_bf16(in ? wv[i] : 0.f, hi, lo);
+            Ws[0][(rr + 8 * i) * PLD + kk] = hi;
+            Ws[1][(rr + 8 * i) * PLD + kk] = lo;
+        }
+    };
+    mfloatx16 acc[2][2];  // [row tile][column tile]
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int c = 64 * w + 32 * nt + l32;
+        const float b = a.bih[c] + a.bhh[c];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = b;
+    }
+    load(0);
+    for (int k0 = 0; k0 < I; k0 += PK) {
+        store(k0);
+        __syncthreads();
+        if (k0 + PK < I) load(k0 + PK);
+#pragma unroll
+        for (int s = 0; s < PK / 16; ++s) {
+            const int ko = 16 * s + 8 * lh;
+            mbf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                ah[t] = *(const mbf16x8*)(&Xs[0][(32 * t + l32) * PLD + ko]);
+                al[t] = *(const mbf16x8*)(&Xs[1][(32 * t + l32) * PLD + ko]);
+                bh[t] = *(const mbf16x8*)(&Ws[0][(64 * w + 32 * t + l32) * PLD + ko]);
+                bl[t] = *(const mbf16x8*)(&Ws[1][(64 * w + 32 * t + l32) * PLD + ko]);
+            }
+#pragma unroll
+            for (int pass = 0; pass < 3; ++pass)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pass == 2 ? al[mt] : ah[mt],
+                                                                              pass == 1 ? bl[nt] : bh[nt],
+                                                                              acc[mt][nt], 0, 0, 0);
+        }
+        __syncthreads();  // every read of this chunk is done before the next one's stores
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = r0 + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (row < M) a.gx[(size_t)row * MG + 64 * w + 32 * nt + l32] = acc[mt][nt][r];
+            }
+}
+
+struct WFwdArgs {
+    int T, B;
+    const float *gx, *whh, *h0, *c0;
+    const uint8_t* reset;
+    float *h_out, *c_out, *gact;
+    float* hp;               // optional: [h_prev | 1] rows [T, B, 65], the backward's operand
+    float *h_save, *c_save;  // optional, as MFwdArgs
+};
+struct WFwdBatch { WFwdArgs m[2]; };
+
+// k_lstm_fwd_mfma8's recurrence (its lane layout, gate arithmetic, resets, tiles and two-step
+// prefetch) with K = the 64 h columns, 2 k-steps per step, and the accumulators started from the
+// env's gx row (8 floats per lane and step, loaded two steps ahead) instead of the bias.
+__global__ __launch_bounds__(512) void k_lstm_fwd_gx8(WFwdBatch ab, int tiles) {
+    __shared__ __attribute__((aligned(16))) mbf16 A[2][2][ME * MLDH];  // [hi, lo][buffer]
+    const WFwdArgs a = ab.m[blockIdx.y];
+    const int T = a.T, B = a.B, RL = MH + 1;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int ebase = blockIdx.x * ME * tiles;
+    if (ebase >= B) return;  // (whole workgroup)
+    const int j = lane & 15, rg = lane >> 4, hj = j >> 3, uu = 8 * w + (j & 7);
+    mbf16x8 wf[2][2][2];  // [hi, lo][tile][k-step]
+    int gr[2];            // the lane's gate row (gx column) per tile
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+        gr[tt] = (2 * tt + hj) * MH + uu;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                mbf16 hi, lo;
+                split_bf16(a.whh[(size_t)gr[tt] * MH + s * 32 + 8 * rg + e], hi, lo);
+                wf[0][tt][s][e] = hi;
+                wf[1][tt][s][e] = lo;
+            }
+    }
+    // the gx values of the lane's accumulators at step t: rows 4 rg .. 4 rg + 3, both tiles
+    // (clamped past T - 1 and B - 1: loaded, never used)
+    auto gload = [&](int e0n, int t, float (&dst)[2][4]) {
+        const size_t tc = (size_t)min(t, T - 1) * B;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const float* row = a.gx + (tc + min(e0n + 4 * rg + p, B - 1)) * MG;
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) dst[tt][p] = row[gr[tt]];
+        }
+    };
+    float pf_h[2], pf_c[2], pf_g[2][4];
+    uint8_t pf_r[2], pf_rn[2];
+    const uint8_t* rbase = a.reset ? a.reset : (const uint8_t*)a.gx;  // masked when absent
+    const float* h0p = a.h0 ? a.h0 : a.gx;
+    const float* c0p = a.c0 ? a.c0 : a.gx;
+    auto in_load = [&](int e0n) {
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+            const int gc = min(e0n + 4 * rg + 2 * hj + pp, B - 1);
+            const float hv = h0p[a.h0 ? (size_t)gc * MH + uu : 0];
+            const float cv = c0p[a.c0 ? (size_t)gc * MH + uu : 0];
+            const uint8_t r0 = rbase[a.reset ? gc : 0];
+            pf_h[pp] = a.h0 ? hv : 0.f;
+            pf_c[pp] = a.c0 ? cv : 0.f;
+            pf_r[pp] = a.reset ? r0 : (uint8_t)0;
+            pf_rn[pp] = rbase[(size_t)min(1, T - 1) * B + gc];
+        }
+        gload(e0n, 0, pf_g);
+    };
+    in_load(ebase);
+    for (int q = 0; q < tiles; ++q) {
+    const int e0 = ebase + q * ME;
+    if (e0 >= B) break;      // (uniform)
+    if (q) __syncthreads();  // the previous tile's last reads of A are done
+    auto put = [&](int buf, int idx, float v) {
+        mbf16 hi, lo;
+        split_bf16(v, hi, lo);
+        A[0][buf][idx] = hi;
+        A[1][buf][idx] = lo;
+    };
+    float c[2], hp[2];
+#pragma unroll
+    for (int pp = 0; pp < 2; ++pp) {
+        const int p = 2 * hj + pp, ge = e0 + 4 * rg + p;
+        const bool rs = a.reset && ge < B && pf_r[pp];
+        const float h0 = ge < B ? pf_h[pp] : 0.f;
+        const float c0 = ge < B ? pf_c[pp] : 0.f;
+        hp[pp] = rs ? 0.f : h0;
+        c[pp] = rs ? 0.f : c0;
+        put(0, (4 * rg + p) * MLDH + uu, hp[pp]);
+        if (a.h_save && ge < B) {
+            a.h_save[(size_t)ge * MH + uu] = hp[pp];
+            a.c_save[(size_t)ge * MH + uu] = c[pp];
+        }
+    }
+    const bool has_reset = a.reset != nullptr;
+    auto rload = [&](int t, uint8_t* r) {
+        const size_t tc = (size_t)min(t, T - 1) * B;
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) r[pp] = rbase[tc + min(e0 + 4 * rg + 2 * hj + pp, B - 1)];
+    };
+    uint8_t rnx[2] = {pf_rn[0], pf_rn[1]};  // reset(t + 1) at step t
+    uint8_t rnx2[2];                          // reset(t + 2)
+    rload(2, rnx2);
+    float gcur[2][4], gnx[2][4], gn2[2][4];  // gx of steps t, t + 1, t + 2
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) gcur[tt][p] = pf_g[tt][p];
+    gload(e0, 1, gnx);
+    // the next tile's inputs, in flight from here (see k_lstm_fwd_mfma8)
+    __builtin_amdgcn_sched_barrier(0);
+    if (q + 1 < tiles && e0 + ME < B) in_load(e0 + ME);
+    __syncthreads();
+    for (int t = 0; t < T; ++t) {
+        const int cur = t & 1;
+        bool rn[2];
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+            rn[pp] = has_reset && t + 1 < T && rnx[pp] != 0;
+            rnx[pp] = rnx2[pp];
+        }
+        rload(t + 3, rnx2);
+        gload(e0, t + 2, gn2);
+        mfloatx4 acc[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) acc[tt][p] = gcur[tt][p];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int o = j * MLDH + s * 32 + 8 * rg;
+            const mbf16x8 ah = *(const mbf16x8*)(&A[0][cur][o]);
+            const mbf16x8 al = *(const mbf16x8*)(&A[1][cur][o]);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[0][tt][s], acc[tt], 0, 0, 0);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[1][tt][s], acc[tt], 0, 0, 0);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][tt][s], acc[tt], 0, 0, 0);
+        }
+        float ownA[2], ownB[2], rcvA[2], rcvB[2];
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+            ownA[pp] = hj ? acc[0][2 + pp] : acc[0][pp];
+            ownB[pp] = hj ? acc[1][2 + pp] : acc[1][pp];
+            rcvA[pp] = ror8(hj ? acc[0][pp] : acc[0][2 + pp]);
+            rcvB[pp] = ror8(hj ? acc[1][pp] : acc[1][2 + pp]);
+        }
+        const int nxt = cur ^ 1;
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+            const int p = 2 * hj + pp, ge = e0 + 4 * rg + p;
+            const float zi = hj ? rcvA[pp] : ownA[pp], zf = hj ? ownA[pp] : rcvA[pp];
+            const float zg = hj ? rcvB[pp] : ownB[pp], zo = hj ? ownB[pp] : rcvB[pp];
+            const float ig = fsig(zi), fg = fsig(zf), gg = ftanh(zg), og = fsig(zo);
+            const float cn = fg * c[pp] + ig * gg;
+            const float hn = og * ftanh(cn);
+            if (ge < B) {
+                const size_t row = (size_t)t * B + ge;
+                if (a.gact) {
+                    float* ga = a.gact + row * MG;
+                    ga[uu] = ig; ga[MH + uu] = fg; ga[2 * MH + uu] = gg; ga[3 * MH + uu] = og;
+                }
+                if (a.c_out) a.c_out[row * MH + uu] = cn;
+                if (a.h_out) a.h_out[row * MH + uu] = hn;
+                if (a.hp) {
+                    a.hp[row * RL + uu] = hp[pp];  // the state this step started from
+                    if (uu == 0) a.hp[row * RL + MH] = 1.f;
+                }
+            }
+            c[pp] = rn[pp] ? 0.f : cn;  // a reset at t + 1 starts that step from zero
+            hp[pp] = rn[pp] ? 0.f : hn;
+            if (t + 1 < T) put(nxt, (4 * rg + p) * MLDH + uu, hp[pp]);
+        }
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                gcur[tt][p] = gnx[tt][p];
+                gnx[tt][p] = gn2[tt][p];
+            }
+        __syncthreads();
+    }
+    }  // tiles
+}
+
+struct WDwArgs {
+    int M, I;
+    const float *dgx, *x;
+    float* slab;  // per row chunk [256 x I], torch row order
+};
+struct WDwBatch { WDwArgs m[2]; };
+
+// dW_ih = dGx^T . x over the M = T B rows: workgroup (row chunk bx of WDR rows, job by, column
+// group bz of WDC x columns) accumulates its [256 x WDC] block on v_mfma_f32_32x32x16_bf16 with
+// the rows as K, 16 per stage (wave w: gate-row tiles 2w, 2w + 1 by 4 column tiles, fp32
+// accumulators over the whole chunk), and writes it into slab row bx.  Both operands are staged
+// transposed (GT[gate][row], XT[column][row]: a fragment is 8 consecutive rows, one 16-byte read)
+// from coalesced element loads issued two stages ahead, double-buffered: one barrier per stage.
+__global__ __launch_bounds__(256) void k_lstm_dwih_wide(WDwBatch ab) {
+    const WDwArgs a = ab.m[blockIdx.y];
+    const int M = a.M, I = a.I;
+    const int m0 = blockIdx.x * WDR, c0 = blockIdx.z * WDC;
+    if (m0 >= M || c0 >= I) return;  // (whole workgroup)
+    __shared__ __attribute__((aligned(16))) mbf16 GT[2][2][MG * ME];   // [hi, lo][buffer]
+    __shared__ __attribute__((aligned(16))) mbf16 XT[2][2][WDC * ME];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int l32 = lane & 31, lh = lane >> 5;
+    const int mend = min(M, m0 + WDR), nst = (mend - m0 + ME - 1) / ME;
+    const int nct = min(WDC / 32, (I - c0 + 31) / 32);  // column tiles in use
+    // thread tid stages gate column tid (16 rows) and x column c0 + (tid & 127), rows 8 xg .. 8 xg + 7
+    const int xc = tid & (WDC - 1), xg = tid >> 7;
+    const bool xin = c0 + xc < I;
+    const int xcol = min(c0 + xc, I - 1);
+    float gv[ME], xv[8];
+    auto load = [&](int st) {
+        const int mb = m0 + st * ME;
+#pragma unroll
+        for (int k = 0; k < ME; ++k) gv[k] = a.dgx[(size_t)min(mb + k, M - 1) * MG + tid];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) xv[k] = a.x[(size_t)min(mb + 8 * xg + k, M - 1) * I + xcol];
+    };
+    auto store = [&](int st, int buf) {
+        const int mb = m0 + st * ME;
+        mbf16x8 hi8, lo8;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                mbf16 hi, lo;
+                split_bf16(mb + 8 * h + k < mend ? gv[8 * h + k] : 0.f, hi, lo);
+                hi8[k] = hi;
+                lo8[k] = lo;
+            }
+            *(mbf16x8*)(&GT[0][buf][tid * ME + 8 * h]) = hi8;
+            *(mbf16x8*)(&GT[1][buf][tid * ME + 8 * h]) = lo8;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            mbf16 hi, lo;
+            split_bf16((xin && mb + 8 * xg + k < mend) ? xv[k] : 0.f, hi, lo);
+            hi8[k] = hi;
+            lo8[k] = lo;
+        }
+        *(mbf16x8*)(&XT[0][buf][xc * ME + 8 * xg]) = hi8;
+        *(mbf16x8*)(&XT[1][buf][xc * ME + 8 * xg]) = lo8;
+    };
+    mfloatx16 dacc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dacc[i][r] = 0.f;
+    load(0);
+    store(0, 0);
+    load(1);  // (clamped past the end)
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        const int buf = st & 1;
+        mbf16x8 ah[2], al[2], bh[4], bl[4];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const int ao = ((2 * w + mt) * 32 + l32) * ME + 8 * lh;
+            ah[mt] = *(const mbf16x8*)(&GT[0][buf][ao]);
+            al[mt] = *(const mbf16x8*)(&GT[1][buf][ao]);
+        }
+#pragma unroll
+        for (int nt = 0; nt < WDC / 32; ++nt) {
+            const int bo = (nt * 32 + l32) * ME + 8 * lh;
+            bh[nt] = *(const mbf16x8*)(&XT[0][buf][bo]);
+            bl[nt] = *(const mbf16x8*)(&XT[1][buf][bo]);
+        }
+        // the other buffer's last reads were stage st - 1's, before its barrier
+        if (st + 1 < nst) store(st + 1, buf ^ 1);
+        load(st + 2);
+#pragma unroll
+        for (int pass = 0; pass < 3; ++pass)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < WDC / 32; ++nt)
+                    if (nt < nct)
+                        dacc[mt * 4 + nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pass == 2 ? al[mt] : ah[mt],
+                                                                                    pass == 1 ? bl[nt] : bh[nt],
+                                                                                    dacc[mt * 4 + nt], 0, 0, 0);
+        __syncthreads();
+    }
+    float* sl = a.slab + (size_t)blockIdx.x * (size_t)MG * I;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < WDC / 32; ++nt) {
+            const int n = c0 + nt * 32 + l32;
+            if (nt >= nct || n >= I) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int g = (2 * w + mt) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                sl[(size_t)g * I + n] = dacc[mt * 4 + nt][r];
+            }
+        }
+}
+
 // ------------------------------------------------------------ recurrent heads --
 // The MLP heads of ActorCriticRecurrent on the LSTM output (rsl_rl actor / critic:
 // Linear(H, N0) -> ELU -> Linear(N0, N1)), fp32, for the fused recurrent optimizer step.
@@ -1767,4 +2179,109 @@ PMLP_API int pmlp_lstm_step_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, 
     hipLaunchKernelGGL(k_lstm_fwd_mfma8<3>, dim3((B + ME * nt - 1) / (ME * nt), njobs), dim3(512), 0, (hipStream_t)stream, a, nt);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_step_mfma_jobs: ") + hipGetErrorString(e));
+}
+
+/* Wide inputs (include/ppo_mlp.h, "wide inputs"): the input projection, the sequence from gx,
+ * the backward on the x-less operand and dW_ih, 1..2 memories per launch. */
+PMLP_API int32_t pmlp_lstm_wide_max_input(void) { return WI_MAX; }
+
+PMLP_API int32_t pmlp_lstm_wide_dw_blocks(int32_t T, int32_t B) {
+    if (T <= 0 || B <= 0) return 0;
+    return (int32_t)(((int64_t)T * B + WDR - 1) / WDR);
+}
+
+enum WideMode { WIDE_FWD, WIDE_BWD, WIDE_STEP };
+
+static int wide_check(const char* w, int njobs, const pmlp_lstm_wide_job* jobs, int T, int B, int H, WideMode mode) {
+    if (njobs < 1 || njobs > 2 || !jobs || T <= 0 || B <= 0) return fail(std::string(w) + ": 1..2 jobs, T, B > 0");
+    if ((int64_t)T * B > INT32_MAX / MG) return fail(std::string(w) + ": T * B * 256 must fit 31 bits");
+    if (H != MH) return fail(std::string(w) + ": hidden 64");
+    for (int i = 0; i < njobs; ++i) {
+        const pmlp_lstm_wide_job& J = jobs[i];
+        if (J.I < WI_MIN || J.I > WI_MAX) return fail(std::string(w) + ": input 65..384");
+        // (every buffer is read and written by element: float alignment is all that is asked)
+        auto bad = [](std::initializer_list<const void*> ps) {
+            for (const void* p : ps)
+                if (!p || ((uintptr_t)p & 3u)) return true;
+            return false;
+        };
+        const bool b = mode == WIDE_FWD
+            ? bad({J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h_out, J.c_out, J.gact, J.gx, J.hp})
+            : mode == WIDE_BWD ? bad({J.x, J.w_hh, J.c_out, J.gact, J.hp, J.dh_out, J.dgx, J.slab, J.slab_ih})
+                               : bad({J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h_out, J.c_out, J.gx});
+        if (b) return fail(std::string(w) + ": null or unaligned buffer");
+        for (const void* p : {(const void*)J.h0, (const void*)J.c0, (const void*)J.h_save, (const void*)J.c_save})
+            if ((uintptr_t)p & 3u) return fail(std::string(w) + ": unaligned h0 / c0 / h_save / c_save");
+        if (mode == WIDE_STEP && (J.h_save == nullptr) != (J.c_save == nullptr))
+            return fail(std::string(w) + ": h_save and c_save together");
+    }
+    return 0;
+}
+
+static int wide_launched(const char* w) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(std::string(w) + ": " + hipGetErrorString(e));
+}
+
+// gx of every job's M rows in one launch
+static void wide_proj(int njobs, const pmlp_lstm_wide_job* jobs, int M, hipStream_t s) {
+    WProjBatch p{};
+    for (int i = 0; i < njobs; ++i) p.m[i] = WProjArgs{M, jobs[i].I, jobs[i].x, jobs[i].w_ih, jobs[i].b_ih, jobs[i].b_hh, jobs[i].gx};
+    hipLaunchKernelGGL(k_lstm_proj_wide, dim3((M + PM - 1) / PM, njobs), dim3(256), 0, s, p);
+}
+
+PMLP_API int pmlp_lstm_fwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t T, int32_t B, int32_t H,
+                                     const uint8_t* reset, void* stream) {
+    const char* w = "pmlp_lstm_fwd_wide_jobs";
+    if (int e = wide_check(w, njobs, jobs, T, B, H, WIDE_FWD)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    wide_proj(njobs, jobs, T * B, s);
+    if (int e = wide_launched(w)) return e;
+    WFwdBatch a{};
+    for (int i = 0; i < njobs; ++i) {
+        const pmlp_lstm_wide_job& J = jobs[i];
+        a.m[i] = WFwdArgs{T, B, J.gx, J.w_hh, J.h0, J.c0, reset, J.h_out, J.c_out, J.gact, J.hp, nullptr, nullptr};
+    }
+    hipLaunchKernelGGL(k_lstm_fwd_gx8, dim3((B + ME - 1) / ME, njobs), dim3(512), 0, s, a, 1);
+    return wide_launched(w);
+}
+
+PMLP_API int pmlp_lstm_bwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t T, int32_t B, int32_t H,
+                                     const uint8_t* reset, void* stream) {
+    const char* w = "pmlp_lstm_bwd_wide_jobs";
+    if (int e = wide_check(w, njobs, jobs, T, B, H, WIDE_BWD)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    MBwdBatch a{};
+    WDwBatch d{};
+    int imax = 0;
+    for (int i = 0; i < njobs; ++i) {
+        const pmlp_lstm_wide_job& J = jobs[i];
+        // (I = 0: the operand rows are [h_prev | 1], the slab [dW_hh | db])
+        a.m[i] = MBwdArgs{T, B, J.w_hh, J.c0, reset, J.c_out, J.gact, J.dh_out, J.dgx, J.hp, 0, J.slab};
+        d.m[i] = WDwArgs{T * B, J.I, J.dgx, J.x, J.slab_ih};
+        imax = std::max(imax, (int)J.I);
+    }
+    hipLaunchKernelGGL((k_lstm_bwd_mfma<3, true>), dim3((B + ME - 1) / ME, njobs), dim3(512), 0, s, a);
+    if (int e = wide_launched(w)) return e;
+    hipLaunchKernelGGL(k_lstm_dwih_wide, dim3(pmlp_lstm_wide_dw_blocks(T, B), njobs, (imax + WDC - 1) / WDC), dim3(256),
+                       0, s, d);
+    return wide_launched(w);
+}
+
+PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t B, int32_t H,
+                                      void* stream) {
+    const char* w = "pmlp_lstm_step_wide_jobs";
+    if (int e = wide_check(w, njobs, jobs, 1, B, H, WIDE_STEP)) return e;
+    hipStream_t s = (hipStream_t)stream;
+    wide_proj(njobs, jobs, B, s);
+    if (int e = wide_launched(w)) return e;
+    WFwdBatch a{};
+    for (int i = 0; i < njobs; ++i) {
+        const pmlp_lstm_wide_job& J = jobs[i];
+        a.m[i] = WFwdArgs{1, B, J.gx, J.w_hh, J.h_out, J.c_out, nullptr, J.h_out, J.c_out, nullptr, nullptr,
+                          J.h_save, J.c_save};
+    }
+    const int nt = step_tiles(B);
+    hipLaunchKernelGGL(k_lstm_fwd_gx8, dim3((B + ME * nt - 1) / (ME * nt), njobs), dim3(512), 0, s, a, nt);
+    return wide_launched(w);
 }

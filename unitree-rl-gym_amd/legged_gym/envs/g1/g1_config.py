@@ -108,3 +108,21 @@ class G1TerrainCfg(G1HeightfieldCfg):
 
     class rewards(G1HeightfieldCfg.rewards):
         ground_relative_heights = True
+
+
+class G1TerrainScanCfg(G1TerrainCfg):
+    """g1_terrain_scan: g1_terrain with the 17 x 11 height scan as the tail of the observation
+    rows (47 / 50 + 187 = 234 / 237 inputs of the recurrent policy's memories: the wide LSTM
+    kernels)."""
+
+    class env(G1TerrainCfg.env):
+        num_observations = 234
+        num_privileged_obs = 237
+
+    class terrain(G1TerrainCfg.terrain):
+        scan_in_observations = True
+
+
+class G1TerrainScanCfgPPO(G1RoughCfgPPO):
+    class runner(G1RoughCfgPPO.runner):
+        experiment_name = "g1_terrain_scan"

@@ -17,6 +17,9 @@ LSTM weight-gradient product, clip_grad_norm_'s per-tensor norms and torch's Ada
         (pmlp_lstm_bwd_dw_mfma_jobs)
     1   every partial (heads, memories) summed into the flat gradient (pmlp_reduce_slabs)
     2   grad-norm partials (+ step / adaptive LR / loss bookkeeping) and Adam
+A memory whose input is wider than 64 columns (an observation row with the height scan) runs on
+the wide kernels instead (pmlp_lstm_fwd_wide_jobs / pmlp_lstm_bwd_wide_jobs: the input projection
+and dW_ih as products of their own, two launches each way).
 Every parameter is a view of ONE flat fp32 buffer (each tensor starting on 16 bytes), the
 gradient a view of another (its 4-float tail: the loss statistics, all-reduced with it at
 world > 1), Adam's moments flat too -- as FusedPPOStep (fused_step.py).
@@ -54,8 +57,10 @@ def supported(ac, num_envs, num_mini_batches):
         return False
     for m in (ac.memory_a, ac.memory_c):
         rnn = m.rnn
+        # (inputs past 64 columns: the wide matrix-core kernels, hidden 64 only)
         if not isinstance(rnn, nn.LSTM) or rnn.num_layers != 1 or not rnn.bias or rnn.batch_first or \
-                rnn.hidden_size not in (32, 64, 128) or rnn.input_size > 64:
+                rnn.hidden_size not in (32, 64, 128) or \
+                rnn.input_size > (lstm_seq.WIDE_MAX_INPUT if rnn.hidden_size == 64 else 64):
             return False
         if rnn.hidden_size != (ac.actor if m is ac.memory_a else ac.critic)[0].in_features:
             return False
@@ -120,8 +125,13 @@ class FusedRecurrentStep:
         self.h_out = [f(T, mb, H) for _ in range(2)]
         self.c_out = [f(T, mb, H) for _ in range(2)]
         self.gact = [f(T, mb, 4 * H) for _ in range(2)]
-        self.xh = [f(T, mb, self.I[n] + H + 1) for n in range(2)]
-        self.dgx = [None if self.mfma_of(n) else f(T, mb, 4 * H) for n in range(2)]
+        # a wide memory (input past 64 columns): gx from the projection kernel, the x-less
+        # operand hp = [h_prev | 1] instead of xh, and dgx for the dW_ih product
+        self.wide = [lstm_seq.wide_usable(r, torch.empty(1, r.input_size)) for r in self.rnns]
+        self.xh = [None if self.wide[n] else f(T, mb, self.I[n] + H + 1) for n in range(2)]
+        self.gx = [f(T, mb, 4 * H) if self.wide[n] else None for n in range(2)]
+        self.hp = [f(T, mb, H + 1) if self.wide[n] else None for n in range(2)]
+        self.dgx = [f(T, mb, 4 * H) if self.wide[n] or not self.mfma_of(n) else None for n in range(2)]
         self.dh = [f(T, mb, H) for _ in range(2)]
         self.y0 = [f(M, self.N0[n]) for n in range(2)]
         self.out = [f(M, self.N1[n]) for n in range(2)]
@@ -138,13 +148,23 @@ class FusedRecurrentStep:
         # row per 16 envs); else the gate gradients and a row-chunked product (lstm_seq._rows_tn)
         L = lstm_seq._lib()
         self.lblk = L.pmlp_lstm_bwd_dw_blocks(mb)
-        self.lrow = [4 * H * (self.I[n] + H + 1) for n in range(2)]
+        self.lrow = [4 * H * ((0 if self.wide[n] else self.I[n]) + H + 1) for n in range(2)]
         self.lslab = [f(self.lblk, self.lrow[n]) if self.mfma[n] else None for n in range(2)]
+        self.wblk = L.pmlp_lstm_wide_dw_blocks(T, mb)
+        self.lslab_ih = [f(self.wblk, 4 * H * self.I[n]) if self.wide[n] else None for n in range(2)]
         red = [mm.ReduceJob(mm._p(self.slab[n]), mm._p(self.grad) + 4 * self._offset[id(self.heads[n][0].weight)],
                             None, self.nh[n], self.nh[n], self.nblk, 0, 0) for n in range(2)]
         for n in range(2):
-            if self.mfma[n]:
-                r = self.rnns[n]
+            r = self.rnns[n]
+            if self.wide[n]:  # [dW_hh | db] rows -> w_hh, b_ih and b_hh; the dW_ih row chunks -> w_ih
+                red.append(mm.ReduceJob(mm._p(self.lslab[n]), mm._p(self.grad) + 4 * self._offset[id(r.weight_hh_l0)],
+                                        None, self.lrow[n], self.lrow[n], self.lblk, 0, 0))
+                red.append(mm.ReduceJob(mm._p(self.lslab[n]) + 4 * 4 * H * H,
+                                        mm._p(self.grad) + 4 * self._offset[id(r.bias_hh_l0)], None, self.lrow[n],
+                                        4 * H, self.lblk, 0, 0))
+                red.append(mm.ReduceJob(mm._p(self.lslab_ih[n]), mm._p(self.grad) + 4 * self._offset[id(r.weight_ih_l0)],
+                                        None, 4 * H * self.I[n], 4 * H * self.I[n], self.wblk, 0, 0))
+            elif self.mfma[n]:
                 red.append(mm.ReduceJob(mm._p(self.lslab[n]), mm._p(self.grad) + 4 * self._offset[id(r.weight_ih_l0)],
                                         None, self.lrow[n], self.lrow[n], self.lblk, 0, 0))
                 red.append(mm.ReduceJob(mm._p(self.lslab[n]) + 4 * 4 * H * (self.I[n] + H),
@@ -161,8 +181,10 @@ class FusedRecurrentStep:
         self.norm_partial = f(int(nparts))
 
     def mfma_of(self, n):
-        return lstm_seq.mfma_usable(self.rnns[n], torch.empty(1, self.rnns[n].input_size)) and \
-            self.rnns[n].input_size + self.H + 1 <= 128
+        """Memory n runs on matrix-core kernels: the narrow form (I + H + 1 <= 128) or the wide one."""
+        x = torch.empty(1, self.rnns[n].input_size)
+        return lstm_seq.wide_usable(self.rnns[n], x) or \
+            (lstm_seq.mfma_usable(self.rnns[n], x) and self.rnns[n].input_size + self.H + 1 <= 128)
 
     def _head_job(self, n):
         s, p = self.heads[n], mm._p
@@ -200,7 +222,17 @@ class FusedRecurrentStep:
         reset = reset.contiguous()
         # 1. the memories over the T steps (zeroing the state where reset[t])
         xs, hids = (obs, cobs), (hid_a, hid_c)
-        both = self.mfma[0] and self.mfma[1]  # both memories in one launch each way
+        wid = [n for n in range(2) if self.wide[n]]  # on the wide kernels, side by side in one launch
+        both = self.mfma[0] and self.mfma[1] and not wid  # both memories in one narrow launch each way
+        if wid:
+            wjobs = (lstm_seq.LstmWideJob * len(wid))()
+            for k, n in enumerate(wid):
+                r, (h0, c0) = self.rnns[n], (t.reshape(mb, H) for t in hids[n])
+                wjobs[k] = lstm_seq.LstmWideJob(self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0),
+                                                P(r.bias_hh_l0), P(r.weight_hh_l0), P(h0), P(c0), P(self.h_out[n]),
+                                                P(self.c_out[n]), P(self.gact[n]), P(self.gx[n]), P(self.hp[n]),
+                                                P(self.dh[n]), P(self.dgx[n]), P(self.lslab[n]), P(self.lslab_ih[n]))
+            lstm_seq._ok(L.pmlp_lstm_fwd_wide_jobs(len(wid), wjobs, T, mb, H, P(reset), st), "pmlp_lstm_fwd_wide_jobs")
         if both:
             jobs = (lstm_seq.LstmJob * 2)()
             for n in range(2):
@@ -209,7 +241,8 @@ class FusedRecurrentStep:
                                            P(r.weight_hh_l0), P(h0), P(c0), P(self.h_out[n]), P(self.c_out[n]),
                                            P(self.gact[n]), P(self.xh[n]), P(self.dh[n]), P(self.lslab[n]))
             lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(2, jobs, T, mb, H, P(reset), st), "pmlp_lstm_fwd_mfma_jobs")
-        for n in range(0 if both else 2):
+        single = [] if both else [n for n in range(2) if not self.wide[n]]  # one launch per memory
+        for n in single:
             r = self.rnns[n]
             h0, c0 = (t.reshape(mb, H) for t in hids[n])
             args = (T, mb, H, self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0), P(r.bias_hh_l0),
@@ -233,7 +266,9 @@ class FusedRecurrentStep:
         # 5. the memories backward, with their weight gradients (slab partials) on the matrix cores
         if both:
             lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma_jobs(2, jobs, T, mb, H, P(reset), st), "pmlp_lstm_bwd_dw_mfma_jobs")
-        for n in range(0 if both else 2):
+        if wid:  # dgx, the [dW_hh | db] slabs and the dW_ih row-chunk partials
+            lstm_seq._ok(L.pmlp_lstm_bwd_wide_jobs(len(wid), wjobs, T, mb, H, P(reset), st), "pmlp_lstm_bwd_wide_jobs")
+        for n in single:
             r, I = self.rnns[n], self.I[n]
             c0 = hids[n][1].reshape(mb, H)
             if self.mfma[n]:

@@ -539,6 +539,10 @@ class RecurrentRollout:
         # (FusedRecurrentStep.mfma, I + H + 1 <= 128), so both always use the same arithmetic.
         rf = alg._rfused
         self.mfma_step = rf is not None and all(rf.mfma)
+        # a wide memory (input past 64 columns) steps on the wide kernels (pmlp_lstm_step_wide_jobs),
+        # its gx row block a static scratch buffer
+        self.wide = list(rf.wide) if self.mfma_step else [False, False]
+        self.gx = [torch.empty(self.N, 4 * rf.H, device=ac.std.device) if w else None for w in self.wide]
         self.heads = None
         # pmlp_act inside the heads' launch where the shapes allow (PMLP_HEADS_ACT=0: two launches)
         self.fuse_act = os.environ.get("PMLP_HEADS_ACT", "1") != "0"
@@ -558,9 +562,17 @@ class RecurrentRollout:
         return mem.hidden_states
 
     def _mstep_pair(self, ma, obs, sa, mc, cobs, sc):
-        """Both memories' Memory.step_ on ONE pmlp_lstm_step_mfma_jobs launch."""
+        """Both memories' Memory.step_ on ONE pmlp_lstm_step_mfma_jobs launch (wide memories: on
+        pmlp_lstm_step_wide_jobs; a narrow actor next to a wide critic: each on its own form)."""
         (ha, ca), (hc, cc) = self._mstate(ma, obs), self._mstate(mc, cobs)
-        return lstm_seq.lstm_step_mfma_pair_([(ma.rnn, obs, ha, ca, sa), (mc.rnn, cobs, hc, cc, sc)])
+        steps = [(ma.rnn, obs, ha, ca, sa), (mc.rnn, cobs, hc, cc, sc)]
+        narrow = [s for s, w in zip(steps, self.wide) if not w]
+        wide = [s + (g,) for s, w, g in zip(steps, self.wide, self.gx) if w]
+        if narrow:
+            lstm_seq.lstm_step_mfma_pair_(narrow)
+        if wide:
+            lstm_seq.lstm_step_wide_pair_(wide)
+        return [ha, hc]
 
     def usable(self, obs, cobs, storage):
         ok = lambda t: (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and  # noqa: E731

@@ -30,6 +30,13 @@ class LstmJob(C.Structure):
                 ("dh_out", C.c_void_p), ("slab", C.c_void_p), ("h_save", C.c_void_p), ("c_save", C.c_void_p)]
 
 
+class LstmWideJob(C.Structure):
+    """include/ppo_mlp.h pmlp_lstm_wide_job: one wide-input memory (64 < I <= 384)."""
+    _fields_ = [("I", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "x", "w_ih", "b_ih", "b_hh", "w_hh", "h0", "c0", "h_out", "c_out", "gact", "gx", "hp", "dh_out", "dgx",
+        "slab", "slab_ih", "h_save", "c_save")]
+
+
 def _lib():
     global _bound
     L = mm.load()
@@ -50,6 +57,12 @@ def _lib():
         L.pmlp_lstm_fwd_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, i32, vp, vp]
         L.pmlp_lstm_bwd_dw_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, i32, vp, vp]
         L.pmlp_lstm_step_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, vp]
+        L.pmlp_lstm_wide_max_input.restype = i32
+        L.pmlp_lstm_wide_dw_blocks.argtypes = [i32, i32]
+        L.pmlp_lstm_wide_dw_blocks.restype = i32
+        L.pmlp_lstm_fwd_wide_jobs.argtypes = [i32, C.POINTER(LstmWideJob), i32, i32, i32, vp, vp]
+        L.pmlp_lstm_bwd_wide_jobs.argtypes = [i32, C.POINTER(LstmWideJob), i32, i32, i32, vp, vp]
+        L.pmlp_lstm_step_wide_jobs.argtypes = [i32, C.POINTER(LstmWideJob), i32, i32, vp]
         _bound = True
     return L
 
@@ -63,6 +76,15 @@ def _ok(status, what):
 # products, fp32 state) for hidden 64 and inputs <= 64; other shapes take the fp32 kernels.
 def mfma_usable(rnn, x):
     return rnn.hidden_size == 64 and x.shape[-1] <= 64
+
+
+# Wider inputs (an observation row with the height scan) at hidden 64: the input projection as
+# its own matrix-core product, then the sequence from gx (pmlp_lstm_*_wide_jobs).
+WIDE_MAX_INPUT = 384  # pmlp_lstm_wide_max_input(): LGS_MAX_OBS + LGS_MAX_SCAN_OBS
+
+
+def wide_usable(rnn, x):
+    return rnn.hidden_size == 64 and 64 < x.shape[-1] <= WIDE_MAX_INPUT
 
 
 def usable(rnn, x):
@@ -106,6 +128,16 @@ class _LSTMDense(torch.autograd.Function):
         xh = torch.empty(T, B, I + H + 1, device=x.device)
         p = mm._p
         ctx.mfma = mfma
+        if mfma and I > 64:  # wide input: projection, then the sequence from gx
+            L = _lib()
+            gx = torch.empty(T, B, 4 * H, device=x.device)
+            hp = torch.empty(T, B, H + 1, device=x.device)
+            job = LstmWideJob(I, p(x), p(w_ih.detach().contiguous()), p(b_ih.detach()), p(b_hh.detach()), p(whh),
+                              p(h0), p(c0), p(h_out), p(c_out), p(gact), p(gx), p(hp))
+            _ok(L.pmlp_lstm_fwd_wide_jobs(1, C.byref(job), T, B, H, p(reset), mm._stream()), "pmlp_lstm_fwd_wide_jobs")
+            ctx.save_for_backward(hp, c0, reset, whh, c_out, gact, x)
+            ctx.I = I
+            return h_out
         if mfma:  # the per-step products on the matrix cores (bf16 operands, fp32 state)
             _ok(_lib().pmlp_lstm_fwd_mfma(T, B, H, I, p(x), p(w_ih.detach().contiguous()), p(b_ih.detach()),
                                           p(b_hh.detach()), p(whh), p(h0), p(c0), p(reset), p(h_out), p(c_out),
@@ -133,6 +165,18 @@ class _LSTMDense(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh_out):
+        if len(ctx.saved_tensors) == 7:  # wide input: the weight gradients as per-workgroup partials
+            hp, c0, reset, whh, c_out, gact, x = ctx.saved_tensors
+            (T, B, H), I, p, L = c_out.shape, ctx.I, mm._p, _lib()
+            dgx = torch.empty(T, B, 4 * H, device=x.device)
+            slab = torch.empty(L.pmlp_lstm_bwd_dw_blocks(B), 4 * H * (H + 1), device=x.device)
+            slab_ih = torch.empty(L.pmlp_lstm_wide_dw_blocks(T, B), 4 * H * I, device=x.device)
+            job = LstmWideJob(I, p(x), None, None, None, p(whh), None, p(c0), None, p(c_out), p(gact), None, p(hp),
+                              p(dh_out.contiguous()), p(dgx), p(slab), p(slab_ih))
+            _ok(L.pmlp_lstm_bwd_wide_jobs(1, C.byref(job), T, B, H, p(reset), mm._stream()), "pmlp_lstm_bwd_wide_jobs")
+            dw = slab.sum(0)
+            db = dw[4 * H * H:].contiguous()
+            return None, None, None, None, slab_ih.sum(0).view(4 * H, I), dw[:4 * H * H].view(4 * H, H), db, db, None
         xh, c0, reset, whh, c_out, gact = ctx.saved_tensors
         I = ctx.I
         T, B, _ = xh.shape
@@ -153,7 +197,8 @@ class _LSTMDense(torch.autograd.Function):
 def lstm_dense(rnn, x, h0, c0, reset, mfma=None):
     """[T,B,I] -> [T,B,H] through rnn (nn.LSTM, one layer) with resets before step t where
     reset[t] != 0; h0/c0 [B,H] (detached: the saved rollout state) or None.  mfma: the
-    matrix-core kernels (default: where mfma_usable)."""
+    matrix-core kernels (default: where mfma_usable or, for inputs past 64 columns, wide_usable;
+    False: the fp32 kernels)."""
     def state(s):
         if s is None:
             return None
@@ -162,7 +207,7 @@ def lstm_dense(rnn, x, h0, c0, reset, mfma=None):
 
     h0, c0 = state(h0), state(c0)
     reset = None if reset is None else reset.to(torch.uint8).contiguous()
-    mfma = mfma_usable(rnn, x) if mfma is None else bool(mfma)
+    mfma = (mfma_usable(rnn, x) or wide_usable(rnn, x)) if mfma is None else bool(mfma)
     return _LSTMDense.apply(x.contiguous(), h0, c0, reset, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0,
                             rnn.bias_hh_l0, mfma)
 
@@ -219,6 +264,24 @@ def lstm_step_mfma_pair_(steps):
     with torch.no_grad():
         _ok(_lib().pmlp_lstm_step_mfma_jobs(len(steps), jobs, B, steps[0][0].hidden_size, mm._stream()),
             "pmlp_lstm_step_mfma_jobs")
+    return [st[2] for st in steps]
+
+
+def lstm_step_wide_pair_(steps):
+    """lstm_step_mfma_pair_ for wide inputs (pmlp_lstm_step_wide_jobs: the dense forward's two
+    kernels at T = 1).  steps: [(rnn, x, h, c, save, gx)] x 1..2, gx [B, 256] a static scratch
+    buffer per memory.  Returns the h buffers."""
+    p = mm._p
+    B = steps[0][1].shape[0]
+    jobs = (LstmWideJob * len(steps))()
+    for n, (rnn, x, h, c, save, gx) in enumerate(steps):
+        hs, cs = (None, None) if save is None else save
+        jobs[n] = LstmWideJob(x.shape[1], p(x), p(rnn.weight_ih_l0), p(rnn.bias_ih_l0), p(rnn.bias_hh_l0),
+                              p(rnn.weight_hh_l0), None, None, p(h), p(c), None, p(gx), None, None, None, None, None,
+                              p(hs), p(cs))
+    with torch.no_grad():
+        _ok(_lib().pmlp_lstm_step_wide_jobs(len(steps), jobs, B, steps[0][0].hidden_size, mm._stream()),
+            "pmlp_lstm_step_wide_jobs")
     return [st[2] for st in steps]
 
 
