@@ -317,6 +317,48 @@ typedef struct lgs_height_obs {
     float noise_scale;   /* noise_scales.height_measurements * noise_level * scale */
 } lgs_height_obs;
 
+/* ---- actuator randomisation and action latency (lgs_set_actuator_randomization) ----
+ * enabled = 1 scales the PD gains of every env and DOF and delays the env's action by whole
+ * physics substeps, inside the control step's decimation loop.  In fp32 without contraction and
+ * in this order, for DOF j of env e (T = the task, D = the model's DOFs):
+ *   kp = (T.p_gains[j] * kp_scale[e][j]) * strength[e][j]
+ *   kd = (T.d_gains[j] * kd_scale[e][j]) * strength[e][j]          (both once per control step)
+ *   a_used(it) = it < delay[e] ? a_prev : a        (substep it = 0 .. decimation - 1; a_prev =
+ *                last_actions[e][j] as the step finds it, 0 in an episode's first step; a = this
+ *                step's clipped action)
+ *   as = a_used * T.action_scale
+ *   control_type P:  t = kp * (target(as) - q) - kd * qd      (target: as + default_dof_pos[j],
+ *                                                              clamped with clamp_pd_targets)
+ *   control_type V:  t = kp * (as - qd) - kd * (qd - last_dof_vel) / dt
+ *   control_type T:  t = as * strength[e][j]
+ *   tau = clip(t, -T.torque_limits[j], T.torque_limits[j])    (record_unclipped_torques as without)
+ * env->actions, the observations' action entries and the action_rate term keep a.  All factors 1
+ * and delay 0 is, bit for bit, the step without the call.
+ * The four buffers are the caller's device memory, read in place by every step (lgs_bind_state's
+ * convention): editing them between steps is supported.  With resample_on_reset an env that
+ * resets -- in a control step, in lgs_reset_idx (mask bytes 1 and 2) or in lgs_reset_all --
+ * redraws its rows, u(k) = lgs_uniform(seed, e, step key, LGS_STREAM_ACTUATOR, k):
+ *   kp_scale[e][j] = (kp_range[1] - kp_range[0]) * u(j) + kp_range[0]
+ *   kd_scale[e][j] = likewise with kd_range and u(LGS_MAX_DOFS + j)
+ *   strength[e][j] = likewise with strength_range and u(2 * LGS_MAX_DOFS + j)
+ *   n = delay_range[1] - delay_range[0] + 1
+ *   delay[e] = delay_range[0] + min((int)(u(3 * LGS_MAX_DOFS) * (float)n), n - 1)
+ * The step in which an env resets ran on its old rows; the new ones act from the next step.
+ * A range [1, 1] draws exactly 1.0f.  This call and lgs_set_task may come in either order: every
+ * step / reset entry point checks the pair (non-NULL buffers, finite ranges with 0 <= lo <= hi,
+ * 0 <= delay lo <= hi <= decimation) and refuses a bad one with LGS_ERR_ARG before any launch.
+ * lgs_simulate (caller-supplied torques) is not affected. */
+typedef struct lgs_actuator_rand {
+    int32_t enabled;            /* 0: the step is what it is without this call */
+    int32_t resample_on_reset;  /* 1: a resetting env redraws its rows; 0: the buffers are only read */
+    float   kp_range[2], kd_range[2], strength_range[2];
+    int32_t delay_range[2];     /* physics substeps, 0 <= lo <= hi <= decimation */
+    float*   kp_scale;          /* device [N, D]  (D = the model's real DOFs, as env->torques) */
+    float*   kd_scale;          /* device [N, D] */
+    float*   strength;          /* device [N, D] */
+    int32_t* delay;             /* device [N] */
+} lgs_actuator_rand;
+
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */
 typedef struct lgs_env_buffers {
     float* actions;          /* [N,A] in: raw policy actions; out: clipped env.actions (0 on reset) */
@@ -480,6 +522,10 @@ LGS_API int lgs_set_heightfield(lgs_sim* sim, const int16_t* heights, int32_t ro
  * enabled = 0: the rows are the layout's own (the default) */
 LGS_API int lgs_set_height_observations(lgs_sim* sim, const lgs_height_obs* desc);
 
+/* per-env, per-DOF PD gain / motor strength factors and a per-env action delay in the control
+ * step (lgs_actuator_rand above).  desc->enabled = 0 turns it off; a NULL sim or desc is an error. */
+LGS_API int lgs_set_actuator_randomization(lgs_sim* sim, const lgs_actuator_rand* desc);
+
 /* create_actor(..., self_collisions, 0) (legged_robot.py:373-374): the self-collision
  * proxies and pairs of every env (host descriptor, copied; NULL or num_pairs = 0: off) */
 LGS_API int lgs_set_self_collision(lgs_sim* sim, const lgs_self_collision_desc* desc);
@@ -537,5 +583,6 @@ LGS_API float lgs_uniform(uint64_t seed, uint32_t env, uint32_t step, uint32_t s
 #define LGS_STREAM_RESET_CMD 4u
 #define LGS_STREAM_PUSH 5u
 #define LGS_STREAM_TERRAIN 6u
+#define LGS_STREAM_ACTUATOR 7u
 
 #endif /* LEGGEDSIM_H */

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -482,6 +483,11 @@ struct Smem {
         float air[LGS_MAX_FEET];
         int lastc[LGS_MAX_FEET];
         float sums[LGS_MAX_REWARDS + 1];
+        // the PD law's per-DOF gains and motor strength of this control step and the env's action
+        // delay in substeps (load_actuator: the task's gains, times the env's factors with
+        // lgs_set_actuator_randomization; strength 1 and delay 0 without)
+        float kp[D > 0 ? D : 1], kd[D > 0 ? D : 1], strength[D > 0 ? D : 1];
+        int delay;
     } pre;
 #ifdef LGS_PHASE_STAMPS
     unsigned long long stamps[LGS_NPHASE];
@@ -2093,6 +2099,76 @@ __device__ __forceinline__ const TerrainTail& terrain_tail(const lgs_task_params
     return *reinterpret_cast<const TerrainTail*>(&T + 1);
 }
 __global__ void k_set_terrain_tail(TerrainTail* dst, TerrainTail v) { *dst = v; }
+
+// ---- actuator randomisation and action latency (include/leggedsim.h, lgs_actuator_rand) ----
+// The caller's factor buffers and the resampling ranges, in device memory after TerrainTail and
+// for its reason: read through the task pointer at the point of use, they hold no SGPR through
+// the physics.  Written by lgs_set_actuator_randomization alone (the pointers are the setter's,
+// not a call's env buffers).
+struct ActuatorTail {
+    float* kp_scale;   // [N, A]
+    float* kd_scale;   // [N, A]
+    float* strength;   // [N, A]
+    int* delay;        // [N]
+    int enabled, resample;
+    float kp_lo, kp_hi, kd_lo, kd_hi, st_lo, st_hi;
+    int dl_lo, dl_hi;
+};
+static_assert(sizeof(TerrainTail) % alignof(ActuatorTail) == 0, "ActuatorTail follows TerrainTail");
+__device__ __forceinline__ const ActuatorTail& actuator_tail(const lgs_task_params& T) {
+    return *reinterpret_cast<const ActuatorTail*>(&terrain_tail(T) + 1);
+}
+
+// The PD law's inputs of this control step into s.pre, issued with the state loads: the gains
+// kp = (p_gain * kp_scale) * strength, kd = (d_gain * kd_scale) * strength, formed once, the
+// strength (the torque mode's factor) and the env's delay.  Without the feature they are the
+// task's gains, 1 and 0, and the substep loop below computes what it always did.  The physics
+// half alone (post == false) fetches the previous actions here; the fused step has them from
+// load_post_inputs.  A padded model's inert DOFs: zero gains, previous action 0.
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_actuator(Smem<D, B, ROWS>& s, const lgs_task_params& T,
+                                              const lgs_env_buffers& E, int e, bool post) {
+    const int lane = hl<EPW>();
+    const int A = T.num_actions;
+    const ActuatorTail& X = actuator_tail(T);
+    const int jd = lane < D ? lane : 0;
+    float kp = T.p_gains[jd], kd = T.d_gains[jd], st = 1.f;
+    int dl = 0;
+    if (X.enabled) {  // (wave-uniform)
+        const size_t r = (size_t)A * e + (lane < A ? lane : 0);
+        const float ks = X.kp_scale[r], ds = X.kd_scale[r], m = X.strength[r];
+        dl = X.delay[e];
+        if (!post) {
+            const float la = E.last_actions[r];
+            if (lane < A) s.pre.last_act[lane] = la;
+        }
+        if (lane < A) { kp = (kp * ks) * m; kd = (kd * ds) * m; st = m; }
+        if (PAD && lane >= A && lane < D) s.pre.last_act[lane] = 0.f;
+    }
+    if (lane < D) { s.pre.kp[lane] = kp; s.pre.kd[lane] = kd; s.pre.strength[lane] = st; }
+    if (lane == 0) s.pre.delay = dl;
+}
+
+// A resetting env redraws its rows (resample_on_reset): lane j its DOF's three factors, lane 0
+// the delay.  Formulas and draw indices: include/leggedsim.h.
+template <int EPW>
+__device__ __forceinline__ void resample_actuator(const lgs_task_params& T, int e, uint32_t step) {
+    const ActuatorTail& X = actuator_tail(T);
+    if (!X.enabled || !X.resample) return;
+    const int lane = hl<EPW>();
+    const int A = T.num_actions;
+    const uint64_t seed = T.seed;
+    if (lane < A) {
+        const size_t r = (size_t)A * e + lane;
+        X.kp_scale[r] = rand_range(X.kp_lo, X.kp_hi, philox_uniform(seed, e, step, LGS_STREAM_ACTUATOR, lane));
+        X.kd_scale[r] = rand_range(X.kd_lo, X.kd_hi, philox_uniform(seed, e, step, LGS_STREAM_ACTUATOR, LGS_MAX_DOFS + lane));
+        X.strength[r] = rand_range(X.st_lo, X.st_hi, philox_uniform(seed, e, step, LGS_STREAM_ACTUATOR, 2 * LGS_MAX_DOFS + lane));
+    }
+    if (lane == 0) {
+        const int n = X.dl_hi - X.dl_lo + 1;
+        X.delay[e] = X.dl_lo + min((int)(philox_uniform(seed, e, step, LGS_STREAM_ACTUATOR, 3 * LGS_MAX_DOFS) * (float)n), n - 1);
+    }
+}
 // legged_gym's _get_heights for this env: the grid points of the task rotated by the base yaw
 // (the yaw-only quaternion (0, 0, qz, qw) normalised: no transcendental), moved to the base,
 // truncated to a map cell, the lowest of the cell's three samples.  One point per lane,
@@ -2363,6 +2439,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         }
         if (lane < A) { act[lane] = 0.f; E.actions[A * e + lane] = 0.f; E.last_actions[A * e + lane] = 0.f; }
         if (lane < T.num_feet) E.feet_air_time[T.num_feet * e + lane] = 0.f;
+        resample_actuator<EPW>(T, e, step);  // (the step's physics ran on the old rows)
         float rv = (lane < 6) ? rand_range(-0.5f, 0.5f, philox_uniform(seed, e, step, LGS_STREAM_RESET_ROOT, lane)) : 0.f;
         // lanes 0-2: the env origin's component.  The level curriculum (the rule and its
         // operation order: include/leggedsim.h, terrain_curriculum) moves it first, on the pre-reset
@@ -2590,6 +2667,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
     float* rbs = (T.write_body_states && st.rbs) ? st.rbs + (size_t)13 * Br * e : nullptr;
     STAMP_INIT();
     if (mode == MODE_STEP || mode == MODE_PHYSICS) {
+        load_actuator<D, B, ROWS, EPW, PAD>(s, T, E, e, mode != MODE_PHYSICS);
         float a = 0.f;
         if (lane < A) {
             const float* ain = E.actions_in ? E.actions_in : E.actions;
@@ -2603,19 +2681,22 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
         float traw = 0.f;  // this DOF lane's PD torque before the effort clip (record_unclipped_torques)
         for (int it = 0; it < T.decimation; ++it) {  // :627-639
             if (lane < D) {  // _compute_torques :649-671
-                const float as = a * T.action_scale;
+                // (the env's action latency, lgs_actuator_rand: the previous step's action for
+                // the first `delay` substeps; the gains and strength: load_actuator)
+                const float as = (it < s.pre.delay ? s.pre.last_act[lane] : a) * T.action_scale;
                 const float q = s.q[lane], qd = s.qd[lane];
+                const float kp = s.pre.kp[lane], kd = s.pre.kd[lane];
                 float t;
                 if (T.control_type == 0 && T.clamp_pd_targets) {  // the clamped target (go2_handstand_env.py:333-349)
                     const float tg = clipf(as + T.default_dof_pos[lane], T.pd_target_lower[lane], T.pd_target_upper[lane]);
-                    t = T.p_gains[lane] * (tg - q) - T.d_gains[lane] * qd;
+                    t = kp * (tg - q) - kd * qd;
                 }
-                else if (T.control_type == 0) t = T.p_gains[lane] * (as + T.default_dof_pos[lane] - q) - T.d_gains[lane] * qd;
+                else if (T.control_type == 0) t = kp * (as + T.default_dof_pos[lane] - q) - kd * qd;
                 else if (T.control_type == 1) {
                     const float lqd = lane < Ad ? s.pre.last_qd[lane] : 0.f;
-                    t = T.p_gains[lane] * (as - qd) - T.d_gains[lane] * (qd - lqd) / sp.dt;
+                    t = kp * (as - qd) - kd * (qd - lqd) / sp.dt;
                 }
-                else t = as;
+                else t = as * s.pre.strength[lane];
                 traw = t;
                 s.tau[lane] = clipf(t, -T.torque_limits[lane], T.torque_limits[lane]);
             }
@@ -2779,6 +2860,8 @@ struct lgs_sim {
     lgs_height_obs hobs{};
     float hf_hs = 0.f;           // the heightfield's horizontal scale (TerrainTail::hf_hs)
     TerrainTail tail_host{};     // what the device block after task_dev holds (sync_terrain_tail)
+    lgs_actuator_rand act{};     // lgs_set_actuator_randomization's descriptor (check_actuator)
+    int task_decimation = 0;     // the task's decimation: the action delay's upper bound
     int epw = 1;    // envs per wave of k_step (2 for a 32-row entry at even N)
     std::vector<std::string> body_names, dof_names;  // name queries (empty when not given)
 };
@@ -3084,8 +3167,9 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
         free(ones);
     }
     static_assert(sizeof(lgs_task_params) % alignof(TerrainTail) == 0, "TerrainTail follows lgs_task_params");
-    HIP_TRY(hipMalloc(&s->task_dev, sizeof(lgs_task_params) + sizeof(TerrainTail)));
-    HIP_TRY(hipMemset(s->task_dev, 0, sizeof(lgs_task_params) + sizeof(TerrainTail)));
+    // (the task, then the two device blocks its kernels read through its pointer)
+    HIP_TRY(hipMalloc(&s->task_dev, sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail)));
+    HIP_TRY(hipMemset(s->task_dev, 0, sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail)));
     *out = s;
     return LGS_OK;
 }
@@ -3296,6 +3380,7 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     s->task_heights = t->measure_heights != 0;
     s->task_obs = t->num_obs; s->task_priv = t->num_privileged_obs; s->task_layout = t->obs_layout;
     s->task_actions = t->num_actions;
+    s->task_decimation = t->decimation;
     s->task_scan = t->measure_heights ? t->num_height_x * t->num_height_y : 0;
     return LGS_OK;
 }
@@ -3310,6 +3395,44 @@ LGS_API int lgs_set_height_observations(lgs_sim* s, const lgs_height_obs* d) {
         v.enabled = 1;
     }
     s->hobs = v;
+    return LGS_OK;
+}
+
+LGS_API int lgs_set_actuator_randomization(lgs_sim* s, const lgs_actuator_rand* d) {
+    if (!s || !d) return set_err(LGS_ERR_ARG, "lgs_set_actuator_randomization: null argument");
+    lgs_actuator_rand v{};
+    if (d->enabled) {
+        v = *d;
+        v.enabled = 1;
+        v.resample_on_reset = d->resample_on_reset != 0;
+    }
+    ActuatorTail t{};
+    t.kp_scale = v.kp_scale; t.kd_scale = v.kd_scale; t.strength = v.strength; t.delay = v.delay;
+    t.enabled = v.enabled; t.resample = v.resample_on_reset;
+    t.kp_lo = v.kp_range[0]; t.kp_hi = v.kp_range[1]; t.kd_lo = v.kd_range[0]; t.kd_hi = v.kd_range[1];
+    t.st_lo = v.strength_range[0]; t.st_hi = v.strength_range[1];
+    t.dl_lo = v.delay_range[0]; t.dl_hi = v.delay_range[1];
+    HIP_TRY(hipStreamSynchronize(s->stream));  // no step may still read the previous block
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(s->task_dev + 1) + sizeof(TerrainTail), &t, sizeof(t),
+                      hipMemcpyHostToDevice));
+    s->act = v;
+    return LGS_OK;
+}
+
+// The actuator descriptor against the task (the two setters may come in either order, so every
+// step / reset entry point checks the pair before it launches anything): a kernel never sees a
+// NULL buffer, a range it cannot draw from or a delay past the decimation loop.
+static int check_actuator(lgs_sim* s, const char* what) {
+    const lgs_actuator_rand& a = s->act;
+    if (!a.enabled) return LGS_OK;
+    if (!a.kp_scale || !a.kd_scale || !a.strength || !a.delay)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": actuator randomization needs kp_scale, kd_scale, strength and delay");
+    for (const float* r : {a.kp_range, a.kd_range, a.strength_range})
+        if (!(r[0] >= 0.f) || !(r[1] >= r[0]) || !(r[1] <= FLT_MAX))
+            return set_err(LGS_ERR_ARG, std::string(what) + ": actuator randomization ranges need finite 0 <= lo <= hi");
+    if (a.delay_range[0] < 0 || a.delay_range[1] < a.delay_range[0] || a.delay_range[1] > s->task_decimation)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": actuator delay_range needs 0 <= lo <= hi <= decimation (" +
+                       std::to_string(s->task_decimation) + ")");
     return LGS_OK;
 }
 
@@ -3380,6 +3503,7 @@ static int launch_step(lgs_sim* s, const lgs_env_buffers* env, int64_t step_coun
                        bool extras = true) {
     if (!s || !env) return set_err(LGS_ERR_ARG, std::string(what) + ": null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, std::string(what) + ": state not bound or task not set");
+    if (const int rc = check_actuator(s, what)) return rc;
     if (const int rc = check_terrain_buffers(s, env, what)) return rc;
     // (an entry's 4 waves/SIMD build: while all envs fit one round of waves)
     const Kernels& k = *s->kern;
@@ -3447,6 +3571,7 @@ LGS_API int lgs_reset_all(lgs_sim* s, const lgs_env_buffers* env, int64_t step_c
     if (!s || !env) return set_err(LGS_ERR_ARG, "null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_all: state not bound or task not set");
     if (const int rc = check_obs_width(s, "lgs_reset_all")) return rc;
+    if (const int rc = check_actuator(s, "lgs_reset_all")) return rc;
     hipLaunchKernelGGL(s->kern->reset_all, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, state_of(s),
                        s->task_dev, *env, s->N, (uint32_t)step_counter, nullptr);
     HIP_TRY(hipGetLastError());
@@ -3456,6 +3581,7 @@ LGS_API int lgs_reset_all(lgs_sim* s, const lgs_env_buffers* env, int64_t step_c
 LGS_API int lgs_reset_idx(lgs_sim* s, const lgs_env_buffers* env, const uint8_t* env_mask, int64_t step_counter) {
     if (!s || !env || !env_mask) return set_err(LGS_ERR_ARG, "lgs_reset_idx: null argument");
     if (!s->root || !s->has_task) return set_err(LGS_ERR_STATE, "lgs_reset_idx: state not bound or task not set");
+    if (const int rc = check_actuator(s, "lgs_reset_idx")) return rc;
     if (const int rc = check_terrain_buffers(s, env, "lgs_reset_idx")) return rc;
     hipLaunchKernelGGL(s->kern->reset_all, dim3(s->N), dim3(WAVE), 0, s->stream, s->md, state_of(s),
                        s->task_dev, *env, s->N, (uint32_t)step_counter, env_mask);

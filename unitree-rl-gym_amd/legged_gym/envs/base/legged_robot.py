@@ -30,7 +30,8 @@ from legged_gym.utils.helpers import class_to_dict
 from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
-from leggedsim.task import build_task_params, check_scan_observations, height_obs_params, terrain_switches
+from leggedsim.task import (actuator_rand_params, build_task_params, check_scan_observations, height_obs_params,
+                            terrain_switches)
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -478,9 +479,30 @@ class LeggedRobot(BaseTask):
         self.sim.set_task(self.task_params)
         self.height_obs = height_obs_params(self)
         self.sim.set_height_observations(self.height_obs)
+        self._build_actuator_randomization()
         self._env_structs = [self._make_env_struct(i) for i in range(2)]
         self._bound = {name: getattr(self, name) for name in self.CALLBACK_BUFFERS}
         self._split_step = bool(self._py_rewards or self._hooks)
+
+    def _build_actuator_randomization(self):
+        """cfg.domain_rand's actuator switches: per-env, per-DOF factors on the PD
+        gains and the motor strength, and a per-env action delay in physics substeps, applied
+        inside the native step.  The tensors are the kernel's own (read in place every step;
+        editing them between steps is supported), neutral until an env's first reset draws its
+        rows (actuator_resample_on_reset); None when every switch is off."""
+        self.actuator_rand = actuator_rand_params(self)
+        self.kp_factors = self.kd_factors = self.motor_strengths = self.action_delay_substeps = None
+        if self.actuator_rand.enabled:
+            N, D, dev = self.num_envs, self.num_dof, self.device
+            self.kp_factors = torch.ones(N, D, dtype=torch.float, device=dev)
+            self.kd_factors = torch.ones(N, D, dtype=torch.float, device=dev)
+            self.motor_strengths = torch.ones(N, D, dtype=torch.float, device=dev)
+            self.action_delay_substeps = torch.zeros(N, dtype=torch.int32, device=dev)
+            R = self.actuator_rand
+            R.kp_scale, R.kd_scale = self.kp_factors.data_ptr(), self.kd_factors.data_ptr()
+            R.strength, R.delay = self.motor_strengths.data_ptr(), self.action_delay_substeps.data_ptr()
+            self.sim.set_actuator_randomization(R, (self.kp_factors, self.kd_factors, self.motor_strengths,
+                                                    self.action_delay_substeps))
 
     def _make_env_struct(self, i):
         E = cabi.EnvBuffers()

@@ -103,6 +103,19 @@ class LeggedRobotCfg(BaseConfig):
         push_robots = True
         push_interval_s = 15
         max_push_vel_xy = 1.0
+        # actuator randomisation inside the native step, all off by default: a factor
+        # per env and joint on the PD gains and on the motor strength, and a per-env delay of the
+        # action in physics substeps (0 .. control.decimation); an env redraws its rows when it
+        # resets unless actuator_resample_on_reset is False (the tensors are then only read)
+        randomize_kp = False
+        kp_range = [0.9, 1.1]
+        randomize_kd = False
+        kd_range = [0.9, 1.1]
+        randomize_motor_strength = False
+        motor_strength_range = [0.9, 1.1]
+        randomize_action_delay = False
+        action_delay_range = [0, 2]
+        actuator_resample_on_reset = True
 
     class rewards:
         class scales:

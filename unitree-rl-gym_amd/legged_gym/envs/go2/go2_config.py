@@ -61,6 +61,18 @@ class GO2TerrainCfg(GO2RoughCfg):
         ground_relative_heights = True
 
 
+class GO2RobustCfg(GO2RoughCfg):
+    """go2_robust: the flat-terrain Go2 task with the actuator randomisation of DESIGN 3.11 on:
+    per-joint PD gains and motor strength within +-10 %, and 0 to 2 physics substeps (0 to 10 ms)
+    of action latency, redrawn for an env at each of its resets."""
+
+    class domain_rand(GO2RoughCfg.domain_rand):
+        randomize_kp = True
+        randomize_kd = True
+        randomize_motor_strength = True
+        randomize_action_delay = True
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -73,3 +85,8 @@ class GO2RoughCfgPPO(LeggedRobotCfgPPO):
 class GO2TerrainCfgPPO(GO2RoughCfgPPO):
     class runner(GO2RoughCfgPPO.runner):
         experiment_name = "go2_terrain"
+
+
+class GO2RobustCfgPPO(GO2RoughCfgPPO):
+    class runner(GO2RoughCfgPPO.runner):
+        experiment_name = "go2_robust"

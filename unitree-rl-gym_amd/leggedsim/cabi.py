@@ -51,6 +51,7 @@ def reward_id(name, task_aliases=None):
 
 STREAM_NOISE, STREAM_CMD, STREAM_RESET_DOF, STREAM_RESET_ROOT, STREAM_RESET_CMD, STREAM_PUSH = range(6)
 STREAM_TERRAIN = 6  # the level curriculum's graduation draw
+STREAM_ACTUATOR = 7  # a resetting env's actuator factors and action delay (lgs_set_actuator_randomization)
 MAX_HEIGHT_POINTS = 32
 MAX_SCAN_OBS = 256  # scan points the observation rows may carry after the head (lgs_set_height_observations)
 HEIGHT_OBS_OFFSET, HEIGHT_OBS_CLIP = 0.5, 1.0  # legged_gym's compute_observations: clip(root_z - 0.5 - heights, -1, 1)
@@ -96,6 +97,15 @@ class SelfCollisionHandle:
         self.desc = SelfCollisionDesc(len(self.body), self.body.ctypes.data_as(i32p), self.caps.ctypes.data_as(f32p),
                                       len(self.pairs) // 2, self.pairs.ctypes.data_as(i32p),
                                       int(sc.max_self_contacts))
+
+
+class ActuatorRand(C.Structure):
+    """lgs_actuator_rand: per-env, per-DOF PD gain / motor strength factors and a per-env action
+    delay in physics substeps; the four buffers are the caller's device memory."""
+    _fields_ = [("enabled", C.c_int32), ("resample_on_reset", C.c_int32),
+                ("kp_range", C.c_float * 2), ("kd_range", C.c_float * 2), ("strength_range", C.c_float * 2),
+                ("delay_range", C.c_int32 * 2),
+                ("kp_scale", C.c_void_p), ("kd_scale", C.c_void_p), ("strength", C.c_void_p), ("delay", C.c_void_p)]
 
 
 class HeightObs(C.Structure):

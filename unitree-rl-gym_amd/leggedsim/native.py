@@ -79,6 +79,9 @@ def load():
     lib.lgs_set_heightfield.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float]
     lib.lgs_set_self_collision.argtypes = [vp, C.POINTER(cabi.SelfCollisionDesc)]
     lib.lgs_set_height_observations.argtypes = [vp, C.POINTER(cabi.HeightObs)]
+    if hasattr(lib, "lgs_set_actuator_randomization"):  # (absent only from pre-round-12 builds used in A/B timing)
+        lib.lgs_set_actuator_randomization.argtypes = [vp, C.POINTER(cabi.ActuatorRand)]
+        lib.lgs_set_actuator_randomization.restype = C.c_int
     if hasattr(lib, "lgs_get_contact_stats"):  # (absent only from pre-round-4 builds used in A/B timing)
         lib.lgs_get_contact_stats.argtypes = [vp, vp, C.c_int32]
         lib.lgs_get_contact_stats.restype = C.c_int
@@ -121,6 +124,7 @@ EXPORTED_SYMBOLS = [
     "lgs_step_deferred", "lgs_step_extras", "lgs_get_push_state",
     "lgs_set_self_collision", "lgs_get_body_name", "lgs_get_dof_name", "lgs_find_body", "lgs_find_dof",
     "lgs_get_contact_stats", "lgs_get_instantiation", "lgs_get_factor_chain", "lgs_set_height_observations",
+    "lgs_set_actuator_randomization",
 ]
 
 
@@ -177,6 +181,13 @@ class Sim:
         self._hobs = desc
         check(self.lib, self.lib.lgs_set_height_observations(self.handle, None if desc is None else C.byref(desc)),
               "lgs_set_height_observations")
+
+    def set_actuator_randomization(self, desc, buffers=()):
+        """Actuator factors and action delay in the control step (a cabi.ActuatorRand).  `buffers`:
+        the tensors behind its four pointers, kept alive here (the step reads them in place)."""
+        self._act, self._act_buffers = desc, tuple(buffers)
+        check(self.lib, self.lib.lgs_set_actuator_randomization(self.handle, C.byref(desc)),
+              "lgs_set_actuator_randomization")
 
     def bind(self, root, dofs, cforce, rbs):
         for t in (root, dofs, cforce, rbs):

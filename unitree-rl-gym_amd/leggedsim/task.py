@@ -209,6 +209,42 @@ def height_obs_params(env) -> cabi.HeightObs:
     return H
 
 
+def actuator_rand_params(env) -> cabi.ActuatorRand:
+    """lgs_actuator_rand of an env's cfg.domain_rand, without its buffers (the env
+    allocates them when `enabled`).  A group that is off passes the neutral range ([1, 1]; delay
+    [0, 0]); every group off: enabled = 0.  A range that is not finite 0 <= lo <= hi, or a delay
+    outside 0 .. control.decimation substeps, is refused."""
+    dr = env.cfg.domain_rand
+    R = cabi.ActuatorRand()
+
+    def factor_range(switch, name):
+        if not bool(getattr(dr, switch, False)):
+            return 1.0, 1.0
+        r = getattr(dr, name)
+        lo, hi = (float(r[0]), float(r[1])) if len(r) == 2 else (np.nan, np.nan)
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 <= lo <= hi):
+            raise ValueError(f"domain_rand.{name} must be [lo, hi] with finite 0 <= lo <= hi, not {list(r)!r}")
+        return lo, hi
+
+    R.kp_range[:] = factor_range("randomize_kp", "kp_range")
+    R.kd_range[:] = factor_range("randomize_kd", "kd_range")
+    R.strength_range[:] = factor_range("randomize_motor_strength", "motor_strength_range")
+    delay = (0, 0)
+    if bool(getattr(dr, "randomize_action_delay", False)):
+        r = dr.action_delay_range
+        dec = int(env.cfg.control.decimation)
+        ok = len(r) == 2 and all(float(x) == int(x) for x in r) and 0 <= int(r[0]) <= int(r[1]) <= dec
+        if not ok:
+            raise ValueError(f"domain_rand.action_delay_range must be [lo, hi] in whole physics substeps with "
+                             f"0 <= lo <= hi <= control.decimation = {dec}, not {list(r)!r}")
+        delay = (int(r[0]), int(r[1]))
+    R.delay_range[:] = delay
+    R.enabled = int(any(bool(getattr(dr, s, False)) for s in
+                        ("randomize_kp", "randomize_kd", "randomize_motor_strength", "randomize_action_delay")))
+    R.resample_on_reset = int(bool(R.enabled and getattr(dr, "actuator_resample_on_reset", True)))
+    return R
+
+
 def _terrain_switches(T, env):
     """The rough-terrain switches: the level curriculum's tile table and threshold, the
     height scan's grid, the ground-relative height terms."""
