@@ -14,7 +14,11 @@ from leggedsim import native  # noqa: E402
 
 NAMES = {1: "fk", 2: "inertia", 3: "bias_rnea", 4: "composite", 5: "mass_matrix+rhs", 6: "cholesky",
          7: "qdd+qf", 8: "limits+contact_detect", 9: "contact_rows_J", 10: "Y=L^-1J^T", 11: "A=YtY", 12: "pgs",
-         13: "z+backsub+cforce", 14: "integrate", 15: "body_states", 16: "post_physics", 17: "store"}
+         13: "z+backsub+cforce", 14: "integrate", 15: "body_states", 16: "post_physics", 17: "store",
+         29: "prologue", 30: "pd"}
+# the table's rows in the order they run: kernel entry to the first substep, the PD section
+# before each substep, the substep's phases, the tail
+ORDER = [29, 30] + list(range(1, 18))
 # sub-stamps: their cycles belong to the phase named first (the table adds them in)
 SUB = {8: {31: "ground candidates"},
        16: {24: "base state/commands/term.", 25: "reward terms", 26: "reward total", 27: "reset",
@@ -41,9 +45,9 @@ def main(task="go2", n=4096):
     own = b.copy()
     for i, sub in SUB.items():
         b[i] = sum(own[k] for k in set(sub) | {i})
-    tot = b[1:18].sum()
+    tot = sum(b[i] for i in ORDER)
     print(f"{task} n={n}: cycles per control step (lane-0 wave view, mean over {rows.shape[0]} waves), decimation {dec}: total {tot:.0f}")
-    for i in range(1, 18):
+    for i in ORDER:
         print(f"  {NAMES[i]:24s} {b[i]:10.0f}  {100 * b[i] / tot:5.1f}%")
         for k, name in SUB.get(i, {}).items():
             print(f"      {name:28s} {own[k]:8.0f}")

@@ -35,7 +35,9 @@
 // deltas per phase into a global [N][LGS_NPHASE] buffer.  Never in the real build.
 // 1..17: the phases; 18..23: the wave timeline; 24..28: post-physics from its start to the
 // end of the base-frame block, the reward terms, the reward total, reset, push + obs build
-// (its noise + store part stays in 16); 31: step 8's ground-candidate loop (the rest in 8)
+// (its noise + store part stays in 16); 31: step 8's ground-candidate loop (the rest in 8);
+// 29: the prologue, kernel entry to the first substep's PD section (model, state, post-physics
+// inputs, actuator rows, action clip); 30: the PD section before each substep
 #define LGS_NPHASE 32
 #ifdef LGS_PHASE_STAMPS
 __device__ unsigned long long* g_phase_buf;
@@ -61,6 +63,7 @@ __device__ unsigned long long* g_phase_buf;
         if (threadIdx.x == 0) {                                                                  \
             s.stamps[18] = _wt0; s.stamps[20] = _wr0;                                            \
             s.stamps[22] = _whw; s.stamps[23] = _wxcc;                                           \
+            s.tlast = _wt0;                                                                      \
         }                                                                                        \
     } while (0)
 // the wave's timeline: shader-clock and 100 MHz real-time stamps at kernel entry and exit,
@@ -146,6 +149,9 @@ struct DevModel {
     const float* bsph;
     const unsigned* chunk32;
     int nch32;
+    // the bytes of the instantiation's ModelCache, built once by lgs_create_sim (k_model_image):
+    // what load_model copies to LDS
+    const uint4* image;
 };
 
 struct DevSim {
@@ -387,8 +393,9 @@ __device__ __forceinline__ void self_tangents(const float* n, float* t1, float* 
 // ------------------------------------------------------------ LDS layout --
 // Model topology/geometry cached in LDS at kernel start: every chain walk and
 // subtree test below is an LDS access instead of a dependent global load.
+// (16-byte aligned and sized: the kernels copy it from the sim's image in 16-byte words)
 template <int D, int B>
-struct ModelCache {
+struct alignas(16) ModelCache {
     int dof[B], depth[B], se[B], dofbody[D > 0 ? D : 1];
     unsigned anc[D > 0 ? D : 1];  // bit i: DOF i is an ancestor-or-self of DOF j (i <= j)
     unsigned char chain[B][MAXD];
@@ -488,6 +495,9 @@ struct Smem {
         // lgs_set_actuator_randomization; strength 1 and delay 0 without)
         float kp[D > 0 ? D : 1], kd[D > 0 ? D : 1], strength[D > 0 ? D : 1];
         int delay;
+        // the PD law's per-DOF task vectors of this launch (load_actuator): default_dof_pos,
+        // torque_limits, pd_target_lower / pd_target_upper; no substep reads the task for them
+        float dflt[D > 0 ? D : 1], tlim[D > 0 ? D : 1], tg_lo[D > 0 ? D : 1], tg_hi[D > 0 ? D : 1];
     } pre;
 #ifdef LGS_PHASE_STAMPS
     unsigned long long stamps[LGS_NPHASE];
@@ -495,9 +505,48 @@ struct Smem {
 #endif
 };
 
-// the whole workgroup fills the block's (shared) model cache
+// The block's (shared) model cache is a copy of the sim's image (DevModel::image), which
+// k_model_image builds once per sim with build_model below: the model's arrays never change
+// after lgs_create_sim (lgs_set_heightfield and lgs_set_self_collision write DevSim alone: the
+// map, the pair records; none of build_model's inputs).  The copy: this lane's 16-byte words,
+// every load issued before the first LDS write, unconditional (a lane beyond the image reads
+// its first word), so that a caller may issue its own loads in between and wait once.
+template <int D, int B>
+struct ModelWords {
+    static constexpr int NV = sizeof(ModelCache<D, B>) / 16, K = (NV + WAVE - 1) / WAVE;
+    static_assert(sizeof(ModelCache<D, B>) % 16 == 0, "the image is copied in 16-byte words");
+    typedef unsigned word __attribute__((ext_vector_type(4)));
+    word v[K];
+};
+template <int D, int B>
+__device__ __forceinline__ ModelWords<D, B> load_model_issue(const DevModel& md) {
+    ModelWords<D, B> w;
+    // (where the kernel keeps DevModel in memory, its pointers load as generic ones: say global)
+    using word = typename ModelWords<D, B>::word;
+    const auto* image = (const __attribute__((address_space(1))) word*)md.image;
+#pragma unroll
+    for (int k = 0; k < w.K; ++k) {
+        const int i = (int)threadIdx.x + WAVE * k;
+        w.v[k] = image[i < w.NV ? i : 0];
+    }
+    return w;
+}
+template <int D, int B>
+__device__ __forceinline__ void load_model_commit(ModelCache<D, B>& c, const ModelWords<D, B>& w) {
+#pragma unroll
+    for (int k = 0; k < w.K; ++k) {
+        const int i = (int)threadIdx.x + WAVE * k;
+        if (i < w.NV) reinterpret_cast<typename ModelWords<D, B>::word*>(&c)[i] = w.v[k];
+    }
+}
 template <int D, int B>
 __device__ __forceinline__ void load_model(ModelCache<D, B>& c, const DevModel& md) {
+    load_model_commit(c, load_model_issue<D, B>(md));
+}
+
+// the model cache from the model's arrays (k_model_image alone; one workgroup of WAVE lanes)
+template <int D, int B>
+__device__ __forceinline__ void build_model(ModelCache<D, B>& c, const DevModel& md) {
     const int lane = threadIdx.x;
     if (lane < B) {
         const int j = md.dof[lane];
@@ -530,6 +579,18 @@ __device__ __forceinline__ void load_model(ModelCache<D, B>& c, const DevModel& 
         c.hi[lane] = md.dof_upper[lane];
         c.vl[lane] = md.dof_velocity[lane];
     }
+}
+// lgs_create_sim, once: the cache as the kernels hold it in LDS, out to the sim's image
+// (padding bytes zero)
+template <int D, int B>
+__global__ __launch_bounds__(WAVE) void k_model_image(DevModel md, uint4* out) {
+    __shared__ ModelCache<D, B> mc;
+    constexpr int NV = ModelWords<D, B>::NV;
+    for (int i = threadIdx.x; i < NV; i += WAVE) reinterpret_cast<uint4*>(&mc)[i] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    build_model(mc, md);
+    __syncthreads();
+    for (int i = threadIdx.x; i < NV; i += WAVE) out[i] = reinterpret_cast<const uint4*>(&mc)[i];
 }
 
 // -------------------------------------------------------------- substep --
@@ -608,7 +669,7 @@ __device__ void substep(Smem<D, B, ROWS>* sm, const ModelCache<D, B>& mc, const 
     const float dt = sp.dt;
     const float idt = 1.0f / dt;  // every per-row / per-force division by dt is a multiply (as the oracle)
 
-    STAMP(0);
+    STAMP(30);  // (the caller's PD section)
     // ---- 1. forward kinematics: joint rotations lane per DOF, then lane b walks root..b
     if (lane < D) axis_angle(mc.ax[mc.dofbody[lane]], s.q[lane], s.u.fk.Ra[lane]);
     __syncthreads();
@@ -1704,17 +1765,41 @@ __device__ void body_states(Smem<D, B, ROWS>& s, const ModelCache<D, B>& mc, flo
     }
 }
 
+// The loaders of a launch's prologue come in two halves.  *_issue: the global loads into
+// registers, every one unconditional (a lane beyond a list reads its first entry; a list that
+// is off reads another valid word), none followed by a use.  *_commit: the values to LDS.
+// k_step issues all of them back to back, the model image included, and only then commits:
+// the wave waits for one round trip, not one per list.
+//
 // PAD: the model may be padded to the kernel's shape (the generic instantiations); else its
 // sizes are the template's and every bound below is a compile-time constant
-template <int D, int B, int ROWS, int EPW, bool PAD = false>
-__device__ __forceinline__ void load_state(Smem<D, B, ROWS>& s, const DevState& st, const DevModel& md, int e) {
+struct StateRegs { float root, qv; };
+template <int D, int EPW, bool PAD = false>
+__device__ __forceinline__ StateRegs load_state_issue(const DevState& st, const DevModel& md, int e) {
     const int Dr = PAD ? md.Dr : D;
     const int lane = hl<EPW>();
-    if (lane < 13) s.root[lane] = st.root[13 * e + lane];
+    // (opaque: no row address formed here is kept live for the stores at the kernel's end)
+    asm volatile("" : "+v"(e));
+    StateRegs r;
+    r.root = st.root[13 * e + (lane < 13 ? lane : 0)];
+    // (a model without DOFs has no such rows: the root's)
+    const float* pq = Dr > 0 ? st.dofs + ((size_t)2 * Dr * e + (lane < 2 * Dr ? lane : 0)) : st.root + 13 * e;
+    r.qv = *pq;
+    return r;
+}
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_state_commit(Smem<D, B, ROWS>& s, const DevModel& md, const StateRegs& r) {
+    const int Dr = PAD ? md.Dr : D;
+    const int lane = hl<EPW>();
+    if (lane < 13) s.root[lane] = r.root;
     if (lane < 2 * D) {  // (a padded model's inert DOFs rest at 0)
-        const float v = lane < 2 * Dr ? st.dofs[(size_t)2 * Dr * e + lane] : 0.f;
+        const float v = lane < 2 * Dr ? r.qv : 0.f;
         if (lane & 1) s.qd[lane >> 1] = v; else s.q[lane >> 1] = v;
     }
+}
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_state(Smem<D, B, ROWS>& s, const DevState& st, const DevModel& md, int e) {
+    load_state_commit<D, B, ROWS, EPW, PAD>(s, md, load_state_issue<D, EPW, PAD>(st, md, e));
 }
 template <int D, int B, int ROWS, int EPW, bool PAD = false>
 __device__ __forceinline__ void store_state(Smem<D, B, ROWS>& s, const DevState& st, const DevModel& md, int e) {
@@ -1730,33 +1815,46 @@ __device__ __forceinline__ void store_state(Smem<D, B, ROWS>& s, const DevState&
 // list reads its first entry), so they issue back to back with the state's and the wave
 // waits for one round trip, not one per list; the physics then covers nothing less.
 // The split parts read here what the physics half and a task's Python callback left.
-template <int D, int B, int ROWS, int EPW, bool PAD = false>
-__device__ __forceinline__ void load_post_inputs(Smem<D, B, ROWS>& s, const lgs_task_params& T,
-                                                 const lgs_env_buffers& E, int N, int e, bool post) {
+struct PostRegs {
+    float la, lq, cm, su, air;
+    long long ep;
+    int lc;
+};
+template <int D, int EPW, bool PAD = false>
+__device__ __forceinline__ PostRegs load_post_inputs_issue(const lgs_task_params& T, const lgs_env_buffers& E, int N,
+                                                           int e, bool post) {
     const int lane = hl<EPW>();
     const int A = T.num_actions, Ad = PAD ? A : D, nf = T.num_feet;
-    if (!post) {  // the physics half alone reads the last DOF velocities (a velocity-mode PD)
-        if (lane < Ad) s.pre.last_qd[lane] = E.last_dof_vel[Ad * e + lane];
-        return;
-    }
+    asm volatile("" : "+v"(e));  // (as load_state_issue)
+    PostRegs r{};
+    r.lq = E.last_dof_vel[Ad * e + (lane < Ad ? lane : 0)];
+    if (!post) return r;  // the physics half alone reads the last DOF velocities (a velocity-mode PD)
     const int nsum = T.num_rewards + (T.has_termination_reward ? 1 : 0);
-    const float la = E.last_actions[A * e + (lane < A ? lane : 0)];
-    const float lq = E.last_dof_vel[Ad * e + (lane < Ad ? lane : 0)];
-    const float cm = E.commands[4 * e + (lane & 3)];
-    const float su = E.episode_sums[(size_t)(lane < nsum ? lane : 0) * N + e];
-    const long long ep = E.episode_length[e];
-    float air = 0.f;
-    int lc = 0;
-    if (nf > 0) {  // (a task without feet binds no such buffers)
-        air = E.feet_air_time[nf * e + (lane < nf ? lane : 0)];
-        lc = E.last_contacts[nf * e + (lane < nf ? lane : 0)];
-    }
-    if (lane < A) s.pre.last_act[lane] = la;
-    if (lane < Ad) s.pre.last_qd[lane] = lq;
-    if (lane < 4) s.pre.cmd[lane] = cm;
-    if (lane < nsum) s.pre.sums[lane] = su;
-    if (lane < nf) { s.pre.air[lane] = air; s.pre.lastc[lane] = lc; }
-    if (lane == 0) s.pre.ep = ep;
+    // (a task without feet binds no such buffers: a word of the env's commands, not committed)
+    const int fi = nf * e + (lane < nf ? lane : 0);
+    const float* pa = nf > 0 ? E.feet_air_time + fi : E.commands + 4 * e;
+    const uint8_t* pc = nf > 0 ? E.last_contacts + fi : reinterpret_cast<const uint8_t*>(E.commands + 4 * e);
+    r.air = *pa;
+    r.lc = *pc;
+    r.la = E.last_actions[A * e + (lane < A ? lane : 0)];
+    r.cm = E.commands[4 * e + (lane & 3)];
+    r.su = E.episode_sums[(size_t)(lane < nsum ? lane : 0) * N + e];
+    r.ep = E.episode_length[e];
+    return r;
+}
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_post_inputs_commit(Smem<D, B, ROWS>& s, const lgs_task_params& T,
+                                                        const PostRegs& r, bool post) {
+    const int lane = hl<EPW>();
+    const int A = T.num_actions, Ad = PAD ? A : D, nf = T.num_feet;
+    if (lane < Ad) s.pre.last_qd[lane] = r.lq;
+    if (!post) return;
+    const int nsum = T.num_rewards + (T.has_termination_reward ? 1 : 0);
+    if (lane < A) s.pre.last_act[lane] = r.la;
+    if (lane < 4) s.pre.cmd[lane] = r.cm;
+    if (lane < nsum) s.pre.sums[lane] = r.su;
+    if (lane < nf) { s.pre.air[lane] = r.air; s.pre.lastc[lane] = r.lc; }
+    if (lane == 0) s.pre.ep = r.ep;
 }
 
 // ---------------------------------------------------------- kernels --------
@@ -2125,27 +2223,50 @@ __device__ __forceinline__ const ActuatorTail& actuator_tail(const lgs_task_para
 // task's gains, 1 and 0, and the substep loop below computes what it always did.  The physics
 // half alone (post == false) fetches the previous actions here; the fused step has them from
 // load_post_inputs.  A padded model's inert DOFs: zero gains, previous action 0.
-template <int D, int B, int ROWS, int EPW, bool PAD = false>
-__device__ __forceinline__ void load_actuator(Smem<D, B, ROWS>& s, const lgs_task_params& T,
-                                              const lgs_env_buffers& E, int e, bool post) {
+// The PD law's per-DOF task vectors (default_dof_pos, torque_limits, the target clamp) go to
+// s.pre with them: the substep loop reads LDS alone, and a later lgs_set_task shows in the next
+// launch.
+struct ActuatorRegs {
+    float kp, kd, ks, ds, m, la, dflt, tlim, tg_lo, tg_hi;
+    int dl;
+};
+template <int D, int EPW>
+__device__ __forceinline__ ActuatorRegs load_actuator_issue(const lgs_task_params& T, const lgs_env_buffers& E, int e,
+                                                            bool post) {
     const int lane = hl<EPW>();
     const int A = T.num_actions;
     const ActuatorTail& X = actuator_tail(T);
     const int jd = lane < D ? lane : 0;
-    float kp = T.p_gains[jd], kd = T.d_gains[jd], st = 1.f;
-    int dl = 0;
-    if (X.enabled) {  // (wave-uniform)
+    ActuatorRegs a{};
+    a.kp = T.p_gains[jd]; a.kd = T.d_gains[jd];
+    a.dflt = T.default_dof_pos[jd]; a.tlim = T.torque_limits[jd];
+    a.tg_lo = T.pd_target_lower[jd]; a.tg_hi = T.pd_target_upper[jd];
+    if (X.enabled) {  // (wave-uniform; the setter's pointers are null without it)
         const size_t r = (size_t)A * e + (lane < A ? lane : 0);
-        const float ks = X.kp_scale[r], ds = X.kd_scale[r], m = X.strength[r];
-        dl = X.delay[e];
-        if (!post) {
-            const float la = E.last_actions[r];
-            if (lane < A) s.pre.last_act[lane] = la;
-        }
-        if (lane < A) { kp = (kp * ks) * m; kd = (kd * ds) * m; st = m; }
+        a.ks = X.kp_scale[r]; a.ds = X.kd_scale[r]; a.m = X.strength[r];
+        a.dl = X.delay[e];
+        if (!post) a.la = E.last_actions[r];
+    }
+    return a;
+}
+template <int D, int B, int ROWS, int EPW, bool PAD = false>
+__device__ __forceinline__ void load_actuator_commit(Smem<D, B, ROWS>& s, const lgs_task_params& T,
+                                                     const ActuatorRegs& a, bool post) {
+    const int lane = hl<EPW>();
+    const int A = T.num_actions;
+    float kp = a.kp, kd = a.kd, st = 1.f;
+    int dl = 0;
+    if (actuator_tail(T).enabled) {  // (wave-uniform)
+        dl = a.dl;
+        if (!post && lane < A) s.pre.last_act[lane] = a.la;
+        if (lane < A) { kp = (kp * a.ks) * a.m; kd = (kd * a.ds) * a.m; st = a.m; }
         if (PAD && lane >= A && lane < D) s.pre.last_act[lane] = 0.f;
     }
-    if (lane < D) { s.pre.kp[lane] = kp; s.pre.kd[lane] = kd; s.pre.strength[lane] = st; }
+    if (lane < D) {
+        s.pre.kp[lane] = kp; s.pre.kd[lane] = kd; s.pre.strength[lane] = st;
+        s.pre.dflt[lane] = a.dflt; s.pre.tlim[lane] = a.tlim;
+        s.pre.tg_lo[lane] = a.tg_lo; s.pre.tg_hi[lane] = a.tg_hi;
+    }
     if (lane == 0) s.pre.delay = dl;
 }
 
@@ -2650,7 +2771,13 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
     Smem<D, B, ROWS>& s = sm[hh<EPW>()];
     const lgs_task_params& T = *Tp;
     const int lane = hl<EPW>();
-    load_model(mc, md);
+    const bool phys = mode == MODE_STEP || mode == MODE_PHYSICS;
+    // (a large model's words, held over the env's loads, went to scratch memory in the padded
+    // 26-DOF build: its copy completes first, one round trip more)
+    constexpr bool HOLD_MODEL = ModelWords<D, B>::K <= 4;
+    ModelWords<D, B> mw;
+    if constexpr (HOLD_MODEL) mw = load_model_issue<D, B>(md);
+    else load_model(mc, md);
 #ifdef LGS_DIAG_MULTISTEP
     // diagnostic build (never the shipped library): LGS_DIAG_MULTISTEP control steps per launch
     // on the same actions, no kernel boundary between them -- what a multi-step rollout kernel
@@ -2660,24 +2787,38 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
     step = step0 + (uint32_t)tt;
     __syncthreads();
 #endif
-    load_state<D, B, ROWS, EPW, PAD>(s, st, md, e);
-    load_post_inputs<D, B, ROWS, EPW, PAD>(s, T, E, N, e, mode != MODE_PHYSICS);
     const int A = T.num_actions;
     const int Ad = PAD ? A : D, Br = PAD ? md.Br : B;  // (unpadded: compile-time bounds)
+    // the prologue's loads, all in flight together: kernel arguments -> the task's scalars and
+    // pointers -> the data (the model image, the env's rows); then the LDS writes
+    const StateRegs sr = load_state_issue<D, EPW, PAD>(st, md, e);
+    const PostRegs pr = load_post_inputs_issue<D, EPW, PAD>(T, E, N, e, mode != MODE_PHYSICS);
+    ActuatorRegs ar{};
+    float ain = 0.f, am = 0.f, mu = 1.f;
+    if (phys) {  // (wave-uniform; the post half binds no such rows)
+        ar = load_actuator_issue<D, EPW>(T, E, e, mode != MODE_PHYSICS);
+        ain = (E.actions_in ? E.actions_in : E.actions)[A * e + (lane < A ? lane : 0)];
+        // (a sim without per-env rows: the env's root, unused)
+        am = *(st.added_mass ? st.added_mass + e : st.root + 13 * e);
+        mu = *(st.friction ? st.friction + e : st.root + 13 * e);
+    }
+    if constexpr (HOLD_MODEL) load_model_commit(mc, mw);
+    load_state_commit<D, B, ROWS, EPW, PAD>(s, md, sr);
+    load_post_inputs_commit<D, B, ROWS, EPW, PAD>(s, T, pr, mode != MODE_PHYSICS);
     float* rbs = (T.write_body_states && st.rbs) ? st.rbs + (size_t)13 * Br * e : nullptr;
     STAMP_INIT();
-    if (mode == MODE_STEP || mode == MODE_PHYSICS) {
-        load_actuator<D, B, ROWS, EPW, PAD>(s, T, E, e, mode != MODE_PHYSICS);
+    if (phys) {
+        load_actuator_commit<D, B, ROWS, EPW, PAD>(s, T, ar, mode != MODE_PHYSICS);
         float a = 0.f;
         if (lane < A) {
-            const float* ain = E.actions_in ? E.actions_in : E.actions;
-            a = clipf(ain[A * e + lane], -T.clip_actions, T.clip_actions);  // :623-624
+            a = clipf(ain, -T.clip_actions, T.clip_actions);  // :623-624
             E.actions[A * e + lane] = a;
             s.act[lane] = a;
         }
-        const float am = st.added_mass ? st.added_mass[e] : 0.f;
-        const float mu = st.friction ? st.friction[e] : 1.f;
+        if (!st.added_mass) am = 0.f;
+        if (!st.friction) mu = 1.f;
         __syncthreads();
+        STAMP(29);
         float traw = 0.f;  // this DOF lane's PD torque before the effort clip (record_unclipped_torques)
         for (int it = 0; it < T.decimation; ++it) {  // :627-639
             if (lane < D) {  // _compute_torques :649-671
@@ -2688,17 +2829,17 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? 
                 const float kp = s.pre.kp[lane], kd = s.pre.kd[lane];
                 float t;
                 if (T.control_type == 0 && T.clamp_pd_targets) {  // the clamped target (go2_handstand_env.py:333-349)
-                    const float tg = clipf(as + T.default_dof_pos[lane], T.pd_target_lower[lane], T.pd_target_upper[lane]);
+                    const float tg = clipf(as + s.pre.dflt[lane], s.pre.tg_lo[lane], s.pre.tg_hi[lane]);
                     t = kp * (tg - q) - kd * qd;
                 }
-                else if (T.control_type == 0) t = kp * (as + T.default_dof_pos[lane] - q) - kd * qd;
+                else if (T.control_type == 0) t = kp * (as + s.pre.dflt[lane] - q) - kd * qd;
                 else if (T.control_type == 1) {
                     const float lqd = lane < Ad ? s.pre.last_qd[lane] : 0.f;
                     t = kp * (as - qd) - kd * (qd - lqd) / sp.dt;
                 }
                 else t = as * s.pre.strength[lane];
                 traw = t;
-                s.tau[lane] = clipf(t, -T.torque_limits[lane], T.torque_limits[lane]);
+                s.tau[lane] = clipf(t, -s.pre.tlim[lane], s.pre.tlim[lane]);
             }
             __syncthreads();
 #ifndef LGS_DIAG_IO_ONLY
@@ -2839,6 +2980,7 @@ struct lgs_sim {
     DevModel md{};
     DevSim sp{};
     void* model_mem = nullptr;
+    uint4* image_mem = nullptr;  // DevModel::image
     float* friction = nullptr;
     float* added_mass = nullptr;
     float* vsim = nullptr;  // [N,2] scratch of the all-env push bookkeeping (DevState::vsim)
@@ -2910,6 +3052,8 @@ struct Kernels {
     void (*simulate)(DevModel, DevSim, DevState, int);
     void (*fk)(DevModel, DevState, int);
     void (*reset_all)(DevModel, DevState, const lgs_task_params*, lgs_env_buffers, int, uint32_t, const uint8_t*);
+    void (*model_image)(DevModel, uint4*);  // the shape's ModelCache, built once per sim (DevModel::image)
+    size_t image_bytes;
 };
 // The builds of k_step an entry has.  EPW2 (the 32-row entries: the row capacity sets the LDS
 // footprint, Y and A): one and two envs per wave.  Else one env per wave: an exact shape at
@@ -2925,6 +3069,8 @@ static Kernels kernels_of() {
     k.simulate = k_simulate<D, B, ROWS, CH, PAD>;
     k.fk = k_fk<D, B, ROWS, CH, PAD>;
     k.reset_all = k_reset_all<D, B, ROWS, CH, PAD>;
+    k.model_image = k_model_image<D, B>;
+    k.image_bytes = sizeof(ModelCache<D, B>);
     return k;
 }
 
@@ -3142,6 +3288,13 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
     md.dof_lower = (const float*)(d + o_lo); md.dof_upper = (const float*)(d + o_hi); md.dof_velocity = (const float*)(d + o_vel);
     md.pt_body = (const int*)(d + o_pb); md.pt_pos = (const float*)(d + o_pp); md.pt_radius = (const float*)(d + o_pr);
     md.bsph = (const float*)(d + o_bs); md.chunk32 = (const unsigned*)(d + o_ch); md.nch32 = nch32;
+    // the kernels' LDS copy of the model, built once (no setter changes an array it is made from)
+    HIP_TRY(hipMalloc(&s->image_mem, s->kern->image_bytes));
+    md.image = nullptr;
+    hipLaunchKernelGGL(s->kern->model_image, dim3(1), dim3(WAVE), 0, nullptr, md, s->image_mem);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    md.image = s->image_mem;
     DevSim& sp = s->sp;
     sp.dt = p->dt; sp.gx = p->gravity[0]; sp.gy = p->gravity[1]; sp.gz = p->gravity[2];
     sp.iters = p->solver_iterations; sp.contact_offset = p->contact_offset; sp.rest_offset = p->rest_offset;
@@ -3177,6 +3330,7 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
 LGS_API int lgs_destroy_sim(lgs_sim* s) {
     if (!s) return LGS_OK;
     (void)hipFree(s->model_mem);
+    (void)hipFree(s->image_mem);
     (void)hipFree(s->friction);
     (void)hipFree(s->added_mass);
     (void)hipFree(s->vsim);
