@@ -359,6 +359,44 @@ typedef struct lgs_actuator_rand {
     int32_t* delay;             /* device [N] */
 } lgs_actuator_rand;
 
+/* ---- observation history (lgs_set_observation_history) ----
+ * Let F be the layout's own policy-row width, what lgs_set_task takes as num_obs without this
+ * call (LGS_OBS_QUADRUPED 12 + 3 A; LGS_OBS_HUMANOID 11 + 3 A; LGS_OBS_HANDSTAND 6 + 3 A +
+ * num_feet), and H = frames.  enabled = 1 makes the policy row of env e after a control step
+ *   [frame(t-H+1) | ... | frame(t-1) | frame(t)]           (oldest first; num_obs = H * F)
+ * where a frame is the F values the observation stage writes without the call: after the noise,
+ * after the handstand's contact-flag flip and after clip_observations, so the history holds what
+ * the policy was shown.  frame(t) uses noise_vec[0 .. F) and LGS_STREAM_NOISE draws 0 .. F)
+ * (the handstand's flips F + j), exactly as without the call: no draw moves, none is added, and
+ * older frames are copied, never re-noised.  The privileged row is untouched in every layout
+ * (the humanoid's P entries; the handstand's P = F noisy frame; the quadruped has none, so its
+ * critic reads the history row).  Everything else the step writes -- rewards, termination,
+ * resets, episode sums, commands, the last_* bookkeeping, the state -- is bit for bit what it
+ * writes without the call.
+ * Episode boundary: the first row an env writes after any reset of that env -- the reset inside
+ * a control step, lgs_reset_idx (mask bytes 1 and 2), lgs_reset_all -- has all H slots equal to
+ * that row's new frame: no zeros, and nothing of the ended episode.
+ * State, the caller's device memory, read and written in place by every step (lgs_bind_state's
+ * convention; editing them between steps is supported):
+ *   history [N, (H-1) * F]  after a step the newest H - 1 frames of the row just written, oldest
+ *                           first: row[F .. H * F).  The next step's older slots come from here,
+ *                           never from an observation buffer (lgs_reset_idx and a caller that
+ *                           does not double-buffer write env->obs in place).
+ *   fill [N] int32          1: history[e] holds the env's running episode; 0: the env's next row
+ *                           fills every slot with its frame (and sets the flag to 1).  A reset
+ *                           writes 0, so zeroed buffers from the caller mean "fill on first write".
+ * This call and lgs_set_task may come in either order: every step / reset entry point checks the
+ * pair -- frames in 2 .. LGS_MAX_OBS_FRAMES, non-NULL buffers, num_obs == frames * F, and no
+ * height observations (lgs_set_height_observations; the two do not combine) -- and refuses a bad
+ * one with LGS_ERR_ARG before any launch.  With enabled = 0, num_obs is the layout's own. */
+#define LGS_MAX_OBS_FRAMES 8
+typedef struct lgs_obs_history {
+    int32_t enabled;     /* 0: the rows are what they are without this call */
+    int32_t frames;      /* H, 2 .. LGS_MAX_OBS_FRAMES */
+    float*   history;    /* device [N, (H-1) * F] */
+    int32_t* fill;       /* device [N] */
+} lgs_obs_history;
+
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */
 typedef struct lgs_env_buffers {
     float* actions;          /* [N,A] in: raw policy actions; out: clipped env.actions (0 on reset) */
@@ -525,6 +563,10 @@ LGS_API int lgs_set_height_observations(lgs_sim* sim, const lgs_height_obs* desc
 /* per-env, per-DOF PD gain / motor strength factors and a per-env action delay in the control
  * step (lgs_actuator_rand above).  desc->enabled = 0 turns it off; a NULL sim or desc is an error. */
 LGS_API int lgs_set_actuator_randomization(lgs_sim* sim, const lgs_actuator_rand* desc);
+
+/* the last `frames` observation frames as the policy row (lgs_obs_history above).
+ * desc->enabled = 0 turns it off; a NULL sim or desc is an error. */
+LGS_API int lgs_set_observation_history(lgs_sim* sim, const lgs_obs_history* desc);
 
 /* create_actor(..., self_collisions, 0) (legged_robot.py:373-374): the self-collision
  * proxies and pairs of every env (host descriptor, copied; NULL or num_pairs = 0: off) */

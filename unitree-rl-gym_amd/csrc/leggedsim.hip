@@ -2217,6 +2217,38 @@ __device__ __forceinline__ const ActuatorTail& actuator_tail(const lgs_task_para
     return *reinterpret_cast<const ActuatorTail*>(&terrain_tail(T) + 1);
 }
 
+// ---- observation history (include/leggedsim.h, lgs_obs_history) ----
+// The caller's history and flag buffers, in device memory after ActuatorTail and for its reason;
+// written by lgs_set_observation_history alone.
+struct ObsHistTail {
+    float* history;  // [N, (frames - 1) * F]
+    int* fill;       // [N]
+    int enabled, frames;
+};
+static_assert(sizeof(ActuatorTail) % alignof(ObsHistTail) == 0, "ObsHistTail follows ActuatorTail");
+__device__ __forceinline__ const ObsHistTail& obs_hist_tail(const lgs_task_params& T) {
+    return *reinterpret_cast<const ObsHistTail*>(&actuator_tail(T) + 1);
+}
+constexpr size_t TASK_BLOCK_BYTES =
+    sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail) + sizeof(ObsHistTail);
+
+// Entry j of the newest frame is c: the row's older slots and the env's new history, slot by
+// slot (two values live).  old[s] = the env's history slot s as the step found it, frames
+// t-H+1+s; the row's slot s takes it and the new history's slot s takes old[s + 1], the last one
+// c.  An env whose history is not live (its first row since a reset) takes c everywhere and
+// loads nothing.  The calling lane owns entry j of every slot: each load of old[s + 1][j]
+// precedes, in its own program order, the store to it, and no lane reads another's store.
+__device__ __forceinline__ void obs_history_entry(float* __restrict__ row, float* __restrict__ hist, int F, int H,
+                                                  int j, float c, bool live) {
+    float cur = live ? hist[j] : c;
+    for (int sl = 0; sl < H - 1; ++sl) {
+        const float nxt = (live && sl + 1 < H - 1) ? hist[(size_t)(sl + 1) * F + j] : c;
+        row[(size_t)sl * F + j] = cur;
+        hist[(size_t)sl * F + j] = nxt;
+        cur = nxt;
+    }
+}
+
 // The PD law's inputs of this control step into s.pre, issued with the state loads: the gains
 // kp = (p_gain * kp_scale) * strength, kd = (d_gain * kd_scale) * strength, formed once, the
 // strength (the torque mode's factor) and the env's delay.  Without the feature they are the
@@ -2610,6 +2642,9 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         __syncthreads();
         if (lane < 6) s.root[7 + lane] = rv;
         if (reset_mode >= RESET_IDS && lane == 0) E.reset[e] = 1;  // reset_buf[env_ids] = 1 (:758)
+        // observation history: the env's next row, written by a later launch, fills every slot
+        // (a control step's own reset reaches its observation stage through s.flags[2], below)
+        if (force_reset && lane == 0 && obs_hist_tail(T).enabled) obs_hist_tail(T).fill[e] = 0;
         if (reset_mode != RESET_ALL) {
             // (strided: two envs per wave leave 32 lanes per env, and a task may have more sums)
             const int nsum = num_sums(T);
@@ -2639,6 +2674,17 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         s.root[8] = rand_range(-T.max_push_vel_xy, T.max_push_vel_xy, philox_uniform(seed, e, step, LGS_STREAM_PUSH, 1));
         if (pushed) atomicOr(pushed + (step & 1u), 1u);  // (few envs per step: the pushed and the reset ones)
     }
+    // observation history (lgs_obs_history): Hn frames per row, 1 without it (wave-uniform).  Lane 0
+    // fetches the env's flag while the frame is formed: live = the history holds this episode;
+    // an env this launch reset is not live, whatever the buffer says
+    // The block behind the task is a cold line here, a scalar round trip on the wave's critical
+    // path (+0.7 us per Go2 launch when every step read it): a row as wide as the layout's own,
+    // known from the task's hot fields, has no history and does not look.
+    const int F0 = T.obs_layout == LGS_OBS_HANDSTAND ? 6 + 3 * Ad + T.num_feet
+                 : (T.obs_layout == LGS_OBS_HUMANOID ? 11 : 12) + 3 * Ad;
+    const int S0 = T.measure_heights ? terrain_tail(T).obs_scan : 0;
+    const int Hn = (T.num_obs - S0 != F0 && obs_hist_tail(T).enabled) ? obs_hist_tail(T).frames : 1;
+    if (Hn > 1 && lane == 0) s.flags[2] = reset ? 0 : obs_hist_tail(T).fill[e];
     // compute_observations: entry i of the row on lane i
     {
         // quadruped obs = tmp[0:O]; humanoid priv = tmp[0:P], obs = tmp[3:3+O]
@@ -2680,23 +2726,33 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
     const int off = (T.obs_layout == LGS_OBS_HUMANOID) ? 3 : 0;
     // S > 0: the last S entries of the rows are the height scan (below); the head keeps its
     // indices, its draws and its arithmetic
-    const int S = T.measure_heights ? terrain_tail(T).obs_scan : 0;
-    for (int i = lane; i < O - S; i += WAVE / EPW) {
+    const int S = S0;
+    // F: the frame, the layout's own row without the scan.  With a history (Hn > 1; O = Hn * F,
+    // S = 0) it is the row's newest slot, and lane l, which forms entries l, l + WAVE / EPW, ...,
+    // moves the same entries of the older slots and of the env's history (obs_history_entry)
+    const int F = Hn == 1 ? O - S : F0;
+    float* const row = E.obs + (size_t)O * e;
+    const int newest = (Hn - 1) * F;
+    const bool live = Hn > 1 && s.flags[2] != 0;
+    for (int i = lane; i < F; i += WAVE / EPW) {
         float x = s.u.post.obs_tmp[off + i];
         if (T.add_noise) x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, i) - 1.f) * T.noise_vec[i];
         if (T.obs_layout == LGS_OBS_HANDSTAND) {
             // a contact flag flips with probability contact_flip_prob (go2_handstand_env.py:157-169);
             // the privileged row is the noisy one (:172)
-            const int j = i - (O - T.num_feet);
+            const int j = i - (F - T.num_feet);
             if (T.add_noise && j >= 0) {
-                const bool flip = philox_uniform(seed, e, step, LGS_STREAM_NOISE, O + j) < T.contact_flip_prob;
+                const bool flip = philox_uniform(seed, e, step, LGS_STREAM_NOISE, F + j) < T.contact_flip_prob;
                 x = ((x > 0.5f) != flip) ? 1.f : 0.f;
             }
             if (P > 0 && E.priv_obs && i < P)
                 E.priv_obs[(size_t)P * e + i] = clipf(x, -T.clip_observations, T.clip_observations);
         }
-        E.obs[(size_t)O * e + i] = clipf(x, -T.clip_observations, T.clip_observations);
+        const float c = clipf(x, -T.clip_observations, T.clip_observations);
+        row[newest + i] = c;
+        if (Hn > 1) obs_history_entry(row, obs_hist_tail(T).history + (size_t)newest * e, F, Hn, i, c, live);
     }
+    if (Hn > 1 && lane == 0) obs_hist_tail(T).fill[e] = 1;  // (lane 0 alone reads and writes the flag)
     if (P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID)
         for (int i = lane; i < P - S; i += WAVE / EPW)
             E.priv_obs[(size_t)P * e + i] = clipf(s.u.post.obs_tmp[i], -T.clip_observations, T.clip_observations);
@@ -3004,6 +3060,8 @@ struct lgs_sim {
     TerrainTail tail_host{};     // what the device block after task_dev holds (sync_terrain_tail)
     lgs_actuator_rand act{};     // lgs_set_actuator_randomization's descriptor (check_actuator)
     int task_decimation = 0;     // the task's decimation: the action delay's upper bound
+    lgs_obs_history ohist{};     // lgs_set_observation_history's descriptor (check_obs_width)
+    int task_feet = 0;           // the task's feet: part of the handstand layout's row
     int epw = 1;    // envs per wave of k_step (2 for a 32-row entry at even N)
     std::vector<std::string> body_names, dof_names;  // name queries (empty when not given)
 };
@@ -3320,9 +3378,9 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
         free(ones);
     }
     static_assert(sizeof(lgs_task_params) % alignof(TerrainTail) == 0, "TerrainTail follows lgs_task_params");
-    // (the task, then the two device blocks its kernels read through its pointer)
-    HIP_TRY(hipMalloc(&s->task_dev, sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail)));
-    HIP_TRY(hipMemset(s->task_dev, 0, sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail)));
+    // (the task, then the three device blocks its kernels read through its pointer)
+    HIP_TRY(hipMalloc(&s->task_dev, TASK_BLOCK_BYTES));
+    HIP_TRY(hipMemset(s->task_dev, 0, TASK_BLOCK_BYTES));
     *out = s;
     return LGS_OK;
 }
@@ -3521,8 +3579,13 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
         return set_err(LGS_ERR_ARG, "lgs_set_task: measure_heights needs 1 <= num_height_x, num_height_y <= 32");
     if (t->ground_relative_heights && !t->measure_heights)
         return set_err(LGS_ERR_ARG, "lgs_set_task: ground_relative_heights needs measure_heights");
-    if (t->obs_layout == LGS_OBS_HANDSTAND && t->num_obs != 6 + 3 * t->num_actions + t->num_feet)
-        return set_err(LGS_ERR_ARG, "lgs_set_task: the handstand layout has 6 + 3 A + num_feet observations");
+    // (a whole number of frames, up to LGS_MAX_OBS_FRAMES: the step entry points hold it to
+    // lgs_set_observation_history's count, 1 without it -- check_obs_width)
+    if (t->obs_layout == LGS_OBS_HANDSTAND) {
+        const int head = 6 + 3 * t->num_actions + t->num_feet;
+        if (t->num_obs < head || t->num_obs % head != 0 || t->num_obs / head > LGS_MAX_OBS_FRAMES)
+            return set_err(LGS_ERR_ARG, "lgs_set_task: the handstand layout has 6 + 3 A + num_feet observations");
+    }
     lgs_task_params tt = *t;  // a padded model's inert DOFs: no gains, no torque, no limits
     for (int j = t->num_actions; j < LGS_MAX_DOFS; ++j) {
         tt.p_gains[j] = tt.d_gains[j] = tt.default_dof_pos[j] = tt.torque_limits[j] = 0.f;
@@ -3535,6 +3598,7 @@ LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     s->task_obs = t->num_obs; s->task_priv = t->num_privileged_obs; s->task_layout = t->obs_layout;
     s->task_actions = t->num_actions;
     s->task_decimation = t->decimation;
+    s->task_feet = t->num_feet;
     s->task_scan = t->measure_heights ? t->num_height_x * t->num_height_y : 0;
     return LGS_OK;
 }
@@ -3573,6 +3637,25 @@ LGS_API int lgs_set_actuator_randomization(lgs_sim* s, const lgs_actuator_rand* 
     return LGS_OK;
 }
 
+LGS_API int lgs_set_observation_history(lgs_sim* s, const lgs_obs_history* d) {
+    if (!s || !d) return set_err(LGS_ERR_ARG, "lgs_set_observation_history: null argument");
+    lgs_obs_history v{};
+    if (d->enabled) {
+        v = *d;
+        v.enabled = 1;
+    }
+    // (a descriptor the entry points will refuse never reaches the device as enabled: the kernels
+    // see the feature off until check_obs_width accepts the pair)
+    const bool ok = v.enabled && v.frames >= 2 && v.frames <= LGS_MAX_OBS_FRAMES && v.history && v.fill;
+    ObsHistTail t{};
+    if (ok) { t.history = v.history; t.fill = v.fill; t.enabled = 1; t.frames = v.frames; }
+    HIP_TRY(hipStreamSynchronize(s->stream));  // no step may still read the previous block
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(s->task_dev + 1) + sizeof(TerrainTail) + sizeof(ActuatorTail), &t,
+                      sizeof(t), hipMemcpyHostToDevice));
+    s->ohist = v;
+    return LGS_OK;
+}
+
 // The actuator descriptor against the task (the two setters may come in either order, so every
 // step / reset entry point checks the pair before it launches anything): a kernel never sees a
 // NULL buffer, a range it cannot draw from or a delay past the decimation loop.
@@ -3594,7 +3677,36 @@ static int check_actuator(lgs_sim* s, const char* what) {
 // either order, so every step / reset entry point checks the pair before it launches anything):
 // without the scan tail the rows fit LGS_MAX_OBS; with it they are exactly the layout's head
 // plus the scan's points.
+// With an observation history (lgs_set_observation_history) the policy row is exactly `frames`
+// of the layout's own rows and carries no scan; without one the handstand layout's row is its
+// own width (lgs_set_task let a whole number of frames through).
+static int check_obs_history(lgs_sim* s, const char* what) {
+    const lgs_obs_history& h = s->ohist;
+    const int A = s->task_actions;
+    const int head = s->task_layout == LGS_OBS_HANDSTAND ? 6 + 3 * A + s->task_feet
+                   : s->task_layout == LGS_OBS_HUMANOID ? 11 + 3 * A : 12 + 3 * A;
+    if (!h.enabled) {
+        if (s->task_layout == LGS_OBS_HANDSTAND && s->task_obs != head)
+            return set_err(LGS_ERR_ARG, std::string(what) + ": the handstand layout has 6 + 3 A + num_feet observations "
+                           "(no observation history set)");
+        return LGS_OK;
+    }
+    if (h.frames < 2 || h.frames > LGS_MAX_OBS_FRAMES)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": observation history: frames " + std::to_string(h.frames) +
+                       " outside 2 .. LGS_MAX_OBS_FRAMES (" + std::to_string(LGS_MAX_OBS_FRAMES) + ")");
+    if (!h.history || !h.fill)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": observation history needs the history and fill buffers");
+    if (s->hobs.enabled)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": observation history and height observations do not combine");
+    if (head > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS || s->task_obs != h.frames * head)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " is not " +
+                       std::to_string(h.frames) + " frames of the layout's head (" + std::to_string(head) + ")");
+    return LGS_OK;
+}
+
 static int check_obs_width(lgs_sim* s, const char* what) {
+    if (const int rc = check_obs_history(s, what)) return rc;
+    if (s->ohist.enabled) return LGS_OK;  // (the rows are frames of the head: checked above)
     if (!s->hobs.enabled) {
         if (s->task_obs > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS)
             return set_err(LGS_ERR_ARG, std::string(what) + ": obs counts exceed LGS_MAX_OBS (no height observations set)");

@@ -97,6 +97,14 @@ def derive_env_spec(cfg, model, sim_dt, obs_layout, hip_dof_indices=(), verbose=
 
 
 def noise_scale_vec(cfg, num_obs, A, obs_layout):
+    # an observation history (env.history_length = H > 1): the frame's vector, tiled
+    H = int(getattr(cfg.env, "history_length", 1))
+    if H > 1 and num_obs % H == 0:
+        return np.tile(_frame_noise_scale_vec(cfg, num_obs // H, A, obs_layout), H)
+    return _frame_noise_scale_vec(cfg, num_obs, A, obs_layout)
+
+
+def _frame_noise_scale_vec(cfg, num_obs, A, obs_layout):
     v = np.zeros(num_obs, dtype=np.float32)
     ns = cfg.noise.noise_scales
     lvl = cfg.noise.noise_level

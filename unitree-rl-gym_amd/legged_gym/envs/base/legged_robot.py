@@ -31,7 +31,7 @@ from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
 from leggedsim.task import (actuator_rand_params, build_task_params, check_scan_observations, height_obs_params,
-                            terrain_switches)
+                            obs_history_params, terrain_switches)
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -480,6 +480,7 @@ class LeggedRobot(BaseTask):
         self.height_obs = height_obs_params(self)
         self.sim.set_height_observations(self.height_obs)
         self._build_actuator_randomization()
+        self._build_observation_history()
         self._env_structs = [self._make_env_struct(i) for i in range(2)]
         self._bound = {name: getattr(self, name) for name in self.CALLBACK_BUFFERS}
         self._split_step = bool(self._py_rewards or self._hooks)
@@ -503,6 +504,24 @@ class LeggedRobot(BaseTask):
             R.strength, R.delay = self.motor_strengths.data_ptr(), self.action_delay_substeps.data_ptr()
             self.sim.set_actuator_randomization(R, (self.kp_factors, self.kd_factors, self.motor_strengths,
                                                     self.action_delay_substeps))
+
+    def _build_observation_history(self):
+        """cfg.env.history_length H > 1: the policy row is the last H frames, oldest
+        first, built by the native step's observation stage.  obs_history [N, (H - 1) * F] is the
+        kernel's own state (the newest H - 1 frames of the last row, obs_buf[:, F:]; read and
+        written in place every step, editing it between steps is supported), _obs_history_fill
+        [N] its per-env flag (0: the env's next row repeats its frame in every slot, as after a
+        reset); None when off.  num_obs_frame = F, the layout's own row width."""
+        self.obs_history_params = obs_history_params(self)
+        self.obs_history = self._obs_history_fill = None
+        R = self.obs_history_params
+        self.num_obs_frame = R.num_frame if R.enabled else getattr(self, "num_obs", None)
+        if R.enabled:
+            N, dev = self.num_envs, self.device
+            self.obs_history = torch.zeros(N, (R.frames - 1) * R.num_frame, dtype=torch.float, device=dev)
+            self._obs_history_fill = torch.zeros(N, dtype=torch.int32, device=dev)
+            R.history, R.fill = self.obs_history.data_ptr(), self._obs_history_fill.data_ptr()
+            self.sim.set_observation_history(R, (self.obs_history, self._obs_history_fill))
 
     def _make_env_struct(self, i):
         E = cabi.EnvBuffers()

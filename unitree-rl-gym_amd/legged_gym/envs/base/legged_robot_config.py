@@ -8,6 +8,10 @@ class LeggedRobotCfg(BaseConfig):
         num_envs = 4096
         num_observations = 48
         num_privileged_obs = None  # not None -> step() also returns critic observations
+        # history_length H > 1: the policy row is the env's last H observation frames,
+        # oldest first, built inside the native step (an episode's first row repeats its frame);
+        # num_observations is then H x the layout's own width.  1: off.
+        history_length = 1
         num_actions = 12
         env_spacing = 3.0          # plane grid spacing [m]
         send_timeouts = True       # extras["time_outs"] for value bootstrapping

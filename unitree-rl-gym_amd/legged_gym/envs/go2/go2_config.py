@@ -73,6 +73,16 @@ class GO2RobustCfg(GO2RoughCfg):
         randomize_action_delay = True
 
 
+class GO2RobustHistoryCfg(GO2RobustCfg):
+    """go2_robust_history: go2_robust with the last 5 observation frames as the policy row
+    (5 x 48 = 240 inputs, oldest frame first), so a feed-forward policy can see the
+    actuator it is driving."""
+
+    class env(GO2RobustCfg.env):
+        history_length = 5
+        num_observations = 240
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -90,3 +100,8 @@ class GO2TerrainCfgPPO(GO2RoughCfgPPO):
 class GO2RobustCfgPPO(GO2RoughCfgPPO):
     class runner(GO2RoughCfgPPO.runner):
         experiment_name = "go2_robust"
+
+
+class GO2RobustHistoryCfgPPO(GO2RobustCfgPPO):
+    class runner(GO2RobustCfgPPO.runner):
+        experiment_name = "go2_robust_history"

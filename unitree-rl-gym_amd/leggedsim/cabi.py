@@ -54,6 +54,7 @@ STREAM_TERRAIN = 6  # the level curriculum's graduation draw
 STREAM_ACTUATOR = 7  # a resetting env's actuator factors and action delay (lgs_set_actuator_randomization)
 MAX_HEIGHT_POINTS = 32
 MAX_SCAN_OBS = 256  # scan points the observation rows may carry after the head (lgs_set_height_observations)
+MAX_OBS_FRAMES = 8  # frames an observation history may stack (lgs_set_observation_history)
 HEIGHT_OBS_OFFSET, HEIGHT_OBS_CLIP = 0.5, 1.0  # legged_gym's compute_observations: clip(root_z - 0.5 - heights, -1, 1)
 
 f32p = C.POINTER(C.c_float)
@@ -112,6 +113,12 @@ class HeightObs(C.Structure):
     """lgs_height_obs: the height scan as the tail of the observation rows."""
     _fields_ = [("enabled", C.c_int32), ("offset", C.c_float), ("clip", C.c_float), ("scale", C.c_float),
                 ("noise_scale", C.c_float)]
+
+
+class ObsHistory(C.Structure):
+    """lgs_obs_history: the last `frames` observation frames as the policy row; the
+    two buffers are the caller's device memory."""
+    _fields_ = [("enabled", C.c_int32), ("frames", C.c_int32), ("history", C.c_void_p), ("fill", C.c_void_p)]
 
 
 class TaskParams(C.Structure):

@@ -82,6 +82,9 @@ def load():
     if hasattr(lib, "lgs_set_actuator_randomization"):  # (absent only from pre-round-12 builds used in A/B timing)
         lib.lgs_set_actuator_randomization.argtypes = [vp, C.POINTER(cabi.ActuatorRand)]
         lib.lgs_set_actuator_randomization.restype = C.c_int
+    if hasattr(lib, "lgs_set_observation_history"):  # (absent only from pre-round-13 builds used in A/B timing)
+        lib.lgs_set_observation_history.argtypes = [vp, C.POINTER(cabi.ObsHistory)]
+        lib.lgs_set_observation_history.restype = C.c_int
     if hasattr(lib, "lgs_get_contact_stats"):  # (absent only from pre-round-4 builds used in A/B timing)
         lib.lgs_get_contact_stats.argtypes = [vp, vp, C.c_int32]
         lib.lgs_get_contact_stats.restype = C.c_int
@@ -124,7 +127,7 @@ EXPORTED_SYMBOLS = [
     "lgs_step_deferred", "lgs_step_extras", "lgs_get_push_state",
     "lgs_set_self_collision", "lgs_get_body_name", "lgs_get_dof_name", "lgs_find_body", "lgs_find_dof",
     "lgs_get_contact_stats", "lgs_get_instantiation", "lgs_get_factor_chain", "lgs_set_height_observations",
-    "lgs_set_actuator_randomization",
+    "lgs_set_actuator_randomization", "lgs_set_observation_history",
 ]
 
 
@@ -188,6 +191,13 @@ class Sim:
         self._act, self._act_buffers = desc, tuple(buffers)
         check(self.lib, self.lib.lgs_set_actuator_randomization(self.handle, C.byref(desc)),
               "lgs_set_actuator_randomization")
+
+    def set_observation_history(self, desc, buffers=()):
+        """The last `frames` observation frames as the policy row (a cabi.ObsHistory).  `buffers`:
+        the tensors behind its two pointers, kept alive here (the step reads and writes them in place)."""
+        self._ohist, self._ohist_buffers = desc, tuple(buffers)
+        check(self.lib, self.lib.lgs_set_observation_history(self.handle, C.byref(desc)),
+              "lgs_set_observation_history")
 
     def bind(self, root, dofs, cforce, rbs):
         for t in (root, dofs, cforce, rbs):

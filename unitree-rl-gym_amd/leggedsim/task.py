@@ -57,7 +57,12 @@ def build_task_params(env) -> cabi.TaskParams:
     T.add_noise = int(bool(env.add_noise))
     # (with the height scan observed the vector's tail is the scan's one scale, in lgs_height_obs:
     # height_obs_params, which also refuses a cfg the tail cannot honour)
-    _put(T.noise_vec, _np(env.noise_scale_vec).reshape(-1)[:env.num_obs - height_obs_params(env).num_points])
+    # (with an observation history it is the newest frame's head: history_noise_head)
+    hist = obs_history_params(env)
+    if hist.enabled:
+        _put(T.noise_vec, history_noise_head(env, hist))
+    else:
+        _put(T.noise_vec, _np(env.noise_scale_vec).reshape(-1)[:env.num_obs - height_obs_params(env).num_points])
     T.max_episode_length = float(env.max_episode_length)
     T.max_episode_length_s = float(env.max_episode_length_s)
     T.resample_interval = int(cfg.commands.resampling_time / env.dt)
@@ -243,6 +248,56 @@ def actuator_rand_params(env) -> cabi.ActuatorRand:
                         ("randomize_kp", "randomize_kd", "randomize_motor_strength", "randomize_action_delay")))
     R.resample_on_reset = int(bool(R.enabled and getattr(dr, "actuator_resample_on_reset", True)))
     return R
+
+
+def obs_frame_width(obs_layout, A, num_feet=0):
+    """The width of a layout's own policy row (one frame of an observation history): what
+    lgs_set_task accepts as num_obs for the layout without a history."""
+    if obs_layout == cabi.OBS_HANDSTAND:
+        return 6 + 3 * A + num_feet
+    return (11 if obs_layout == cabi.OBS_HUMANOID else 12) + 3 * A
+
+
+def obs_history_params(env) -> cabi.ObsHistory:
+    """lgs_obs_history of an env's cfg.env.history_length, without its buffers (the env
+    allocates them when `enabled`).  1 is off.  With H >= 2 the policy row is the last H frames,
+    oldest first, each the layout's own row; `num_frame` (not a field of the C struct) is that
+    row's width.  Refused: a length outside 1 .. 8, num_observations that is not H frames, the
+    height scan in the rows (the two do not combine yet), and a task class with a Python
+    compute_observations (it would edit a row whose older frames the kernel has already stored)."""
+    R = cabi.ObsHistory()
+    R.num_frame = 0
+    H = getattr(env.cfg.env, "history_length", 1)
+    if isinstance(H, bool) or int(H) != H or not 1 <= H <= cabi.MAX_OBS_FRAMES:
+        raise ValueError(f"env.history_length must be a whole number of frames from 1 (off) to "
+                         f"{cabi.MAX_OBS_FRAMES}, not {H!r}")
+    H = int(H)
+    if H == 1:
+        return R
+    F = obs_frame_width(env.obs_layout, env.num_actions, len(_np(env.feet_indices).reshape(-1)))
+    if env.cfg.env.num_observations != H * F:
+        raise ValueError(f"env.history_length = {H}: env.num_observations must be {H} x the layout's {F} = "
+                         f"{H * F}, not {env.cfg.env.num_observations}")
+    if scan_in_observations(env.cfg):
+        raise ValueError("env.history_length > 1 and terrain.scan_in_observations do not combine: a history "
+                         "of rows with the height scan is wider than every policy kernel")
+    if "compute_observations" in getattr(env, "_hooks", frozenset()):
+        raise ValueError("env.history_length > 1 with a Python compute_observations: the override would edit "
+                         "a row whose older frames the kernel has already stored (INTEGRATION.md)")
+    R.enabled, R.frames, R.num_frame = 1, H, F
+    return R
+
+
+def history_noise_head(env, R):
+    """The one frame's noise scales of env.noise_scale_vec under an observation history R: the
+    vector is that head tiled R.frames times (older frames are copied, never re-noised, so the
+    kernel reads the head alone); an override that is not that tiling is refused."""
+    v = _np(env.noise_scale_vec).astype(np.float32).reshape(-1)
+    F, H = R.num_frame, R.frames
+    if len(v) != H * F or not (v.reshape(H, F) == v[:F]).all():
+        raise ValueError(f"_get_noise_scale_vec: with env.history_length = {H} the vector must be the frame's "
+                         f"{F} scales tiled {H} times (the kernel noises the newest frame only)")
+    return v[:F]
 
 
 def _terrain_switches(T, env):
