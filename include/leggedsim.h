@@ -307,7 +307,9 @@ typedef struct lgs_task_params {
  * order: a reset env observes one row of heights from where its last episode ended).
  * Needs measure_heights and a layout other than LGS_OBS_HANDSTAND; head <= LGS_MAX_OBS and
  * P <= LGS_MAX_SCAN_OBS.  This call and lgs_set_task may come in either order: the pair is checked
- * by every step / reset entry point, which refuses an inconsistent one before any launch. */
+ * by every step / reset entry point, which refuses an inconsistent one before any launch.
+ * With an observation history (lgs_obs_history below) the scan follows the H frames of the head:
+ * num_obs = H * head + P, entry H * head + k, and the draw stays head + k. */
 #define LGS_MAX_SCAN_OBS 256
 typedef struct lgs_height_obs {
     int32_t enabled;
@@ -386,9 +388,21 @@ typedef struct lgs_actuator_rand {
  *                           fills every slot with its frame (and sets the flag to 1).  A reset
  *                           writes 0, so zeroed buffers from the caller mean "fill on first write".
  * This call and lgs_set_task may come in either order: every step / reset entry point checks the
- * pair -- frames in 2 .. LGS_MAX_OBS_FRAMES, non-NULL buffers, num_obs == frames * F, and no
- * height observations (lgs_set_height_observations; the two do not combine) -- and refuses a bad
- * one with LGS_ERR_ARG before any launch.  With enabled = 0, num_obs is the layout's own. */
+ * pair -- frames in 2 .. LGS_MAX_OBS_FRAMES, non-NULL buffers, num_obs == frames * F -- and
+ * refuses a bad one with LGS_ERR_ARG before any launch.  With enabled = 0, num_obs is the
+ * layout's own.
+ * With the height observations (lgs_set_height_observations, P points, the three
+ * setters in any order) the row is a history of the head alone, then one scan:
+ *   [frame(t-H+1) | ... | frame(t) | scan(t)]                        (num_obs = H * F + P)
+ * The frames follow every rule above with history and fill unchanged in shape and meaning; the
+ * scan is lgs_height_obs's tail, current and never stored.  Scan point k keeps LGS_STREAM_NOISE
+ * draw F + k, its index without a history, so the newest frame and the scan are bit for bit the
+ * entries of the same env without this call.  The humanoid's privileged row stays its head + P.
+ * The entry points accept the pair under the height observations' own rules (a task that measures
+ * heights, P <= LGS_MAX_SCAN_OBS, the quadruped or humanoid layout) with num_obs == H * F + P;
+ * both set on a task without a scan, or any other width, is refused ("observation history and
+ * height observations do not combine", then what num_obs is and would have to be).
+ * lgs_set_task itself takes num_obs up to LGS_MAX_OBS_FRAMES * LGS_MAX_OBS + LGS_MAX_SCAN_OBS. */
 #define LGS_MAX_OBS_FRAMES 8
 typedef struct lgs_obs_history {
     int32_t enabled;     /* 0: the rows are what they are without this call */

@@ -322,7 +322,10 @@ PMLP_API int pmlp_permutation(int64_t* out, int64_t n, uint64_t seed, void* stre
  * chip (LDS) between layers.  Optional stores: xa = the bf16 input rows [M, K0] and y[l] = the
  * bf16 hidden outputs (the backward's operands).  Bitwise equal to the per-layer pmlp_gemm
  * forward (FWD_HIDDEN x3 with the af operand form, FWD_OUT).  Limits: K0 a multiple of 16,
- * <= 256; N0, N2 <= 512 and N1 <= 256, multiples of 32; N3 <= 32; 1..2 jobs.              */
+ * <= 256, or a multiple of 64, 256 < K0 <= 512 (a history of frames in front of a height scan:
+ * the input rows then share an LDS region of Y0's row stride with y1, 32 rows per workgroup, 64
+ * for the update's mini-batches); N0, N2 <= 512 and N1 <= 256, multiples of 32; N3 <= 32;
+ * 1..2 jobs (of either width class).                                                       */
 typedef struct {
     const float* x;
     const int64_t* rows;
@@ -437,8 +440,12 @@ PMLP_API int pmlp_ppo_loss_step(const float* mu, const float* stdv, const float*
  * partials sum 96-row groups, so the logged losses and the std gradient round differently
  * from the 64-row groups of pmlp_ppo_loss_step).  Applies when
  * pmlp_mlp_forward_ppo_loss_parts(M, A) > 0 (M >= 18432, A a multiple of 4 <= 16) and
- * Ap <= 16, a multiple of 4; replaces PPO.update's separate forward and loss launches.   */
+ * Ap <= 16, a multiple of 4; replaces PPO.update's separate forward and loss launches.
+ * With a job of K0 > 256 the workgroups own 64 rows, not 96 (96 rows of y0 leave no room for
+ * input rows that wide), and write pmlp_mlp_forward_ppo_loss_parts_k0(M, A, K0) partials, K0 the
+ * widest job's: pmlp_ppo_loss_step_parts' count and grouping of rows.                      */
 PMLP_API int32_t pmlp_mlp_forward_ppo_loss_parts(int32_t M, int32_t A);
+PMLP_API int32_t pmlp_mlp_forward_ppo_loss_parts_k0(int32_t M, int32_t A, int32_t K0);
 PMLP_API int pmlp_mlp_forward_ppo_loss(const pmlp_mlp_fwd_job* jobs, int32_t M, const float* stdv,
                                        const float* actions, const float* old_logp, const float* old_mu,
                                        const float* old_sigma, const float* adv, const float* ret,

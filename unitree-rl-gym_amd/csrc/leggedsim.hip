@@ -2727,9 +2727,10 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
     // S > 0: the last S entries of the rows are the height scan (below); the head keeps its
     // indices, its draws and its arithmetic
     const int S = S0;
-    // F: the frame, the layout's own row without the scan.  With a history (Hn > 1; O = Hn * F,
-    // S = 0) it is the row's newest slot, and lane l, which forms entries l, l + WAVE / EPW, ...,
-    // moves the same entries of the older slots and of the env's history (obs_history_entry)
+    // F: the frame, the layout's own row without the scan.  With a history (Hn > 1; O = Hn * F + S:
+    // the frames, then the one current scan) it is the row's newest slot, and lane l,
+    // which forms entries l, l + WAVE / EPW, ..., moves the same entries of the older slots and of
+    // the env's history (obs_history_entry).  The scan's lanes touch row[Hn * F ..) alone.
     const int F = Hn == 1 ? O - S : F0;
     float* const row = E.obs + (size_t)O * e;
     const int newest = (Hn - 1) * F;
@@ -2769,7 +2770,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
             const float h = clipf(rz - mh[k], -X.obs_clip, X.obs_clip) * X.obs_scale;
             float x = h;
             if (T.add_noise)
-                x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, O - S + k) - 1.f) * X.obs_noise;
+                x += (2.f * philox_uniform(seed, e, step, LGS_STREAM_NOISE, F + k) - 1.f) * X.obs_noise;
             E.obs[(size_t)O * e + (O - S) + k] = clipf(x, -T.clip_observations, T.clip_observations);
             if (priv) E.priv_obs[(size_t)P * e + (P - S) + k] = clipf(h, -T.clip_observations, T.clip_observations);
         }
@@ -3552,9 +3553,11 @@ LGS_API int lgs_set_dof_state_indexed(lgs_sim* s, const float* src, const int32_
 LGS_API int lgs_set_task(lgs_sim* s, const lgs_task_params* t) {
     if (!s || !t) return set_err(LGS_ERR_ARG, "null argument");
     if (t->num_actions != s->D) return set_err(LGS_ERR_ARG, "lgs_set_task: num_actions must equal num_dofs");
-    // (the rows may carry the height scan after a head of <= LGS_MAX_OBS entries: the step entry
-    // points check the widths against lgs_set_height_observations, check_obs_width)
-    if (t->num_obs < 0 || t->num_privileged_obs < 0 || t->num_obs > LGS_MAX_OBS + LGS_MAX_SCAN_OBS ||
+    // (the rows may carry the height scan after a head of <= LGS_MAX_OBS entries, the policy row
+    // up to LGS_MAX_OBS_FRAMES such heads in front of it: the step entry points check the widths
+    // against lgs_set_height_observations and lgs_set_observation_history, check_obs_width)
+    if (t->num_obs < 0 || t->num_privileged_obs < 0 ||
+        t->num_obs > LGS_MAX_OBS_FRAMES * LGS_MAX_OBS + LGS_MAX_SCAN_OBS ||
         t->num_privileged_obs > LGS_MAX_OBS + LGS_MAX_SCAN_OBS || t->num_rewards > LGS_MAX_REWARDS ||
         t->num_extra_sums < 0 || t->num_rewards + 1 + t->num_extra_sums > WAVE - 1)
         return set_err(LGS_ERR_ARG, "lgs_set_task: obs/reward counts exceed limits");
@@ -3678,8 +3681,9 @@ static int check_actuator(lgs_sim* s, const char* what) {
 // without the scan tail the rows fit LGS_MAX_OBS; with it they are exactly the layout's head
 // plus the scan's points.
 // With an observation history (lgs_set_observation_history) the policy row is exactly `frames`
-// of the layout's own rows and carries no scan; without one the handstand layout's row is its
-// own width (lgs_set_task let a whole number of frames through).
+// of the layout's own rows, then the scan's points when the height observations are set too
+// (check_obs_width holds that pair to the scan's own rules); without one the
+// handstand layout's row is its own width (lgs_set_task let a whole number of frames through).
 static int check_obs_history(lgs_sim* s, const char* what) {
     const lgs_obs_history& h = s->ohist;
     const int A = s->task_actions;
@@ -3696,8 +3700,16 @@ static int check_obs_history(lgs_sim* s, const char* what) {
                        " outside 2 .. LGS_MAX_OBS_FRAMES (" + std::to_string(LGS_MAX_OBS_FRAMES) + ")");
     if (!h.history || !h.fill)
         return set_err(LGS_ERR_ARG, std::string(what) + ": observation history needs the history and fill buffers");
-    if (s->hobs.enabled)
-        return set_err(LGS_ERR_ARG, std::string(what) + ": observation history and height observations do not combine");
+    if (s->hobs.enabled) {  // the pair: a task without a scan, or a row that is not the frames then the scan
+        const int P = s->task_scan;
+        if (P < 1 || s->task_obs != h.frames * head + P)
+            return set_err(LGS_ERR_ARG, std::string(what) + ": observation history and height observations do not combine: " +
+                           (P < 1 ? std::string("the task measures no heights; ") : std::string()) + "num_obs is " +
+                           std::to_string(s->task_obs) + ", the pair needs " + std::to_string(h.frames) +
+                           " frames of the layout's head (" + std::to_string(head) + ") + the scan's points" +
+                           (P < 1 ? std::string() : " (" + std::to_string(P) + ") = " + std::to_string(h.frames * head + P)));
+        return LGS_OK;  // (the scan's own limits, the layout and the privileged row: check_obs_width)
+    }
     if (head > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS || s->task_obs != h.frames * head)
         return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " is not " +
                        std::to_string(h.frames) + " frames of the layout's head (" + std::to_string(head) + ")");
@@ -3706,8 +3718,8 @@ static int check_obs_history(lgs_sim* s, const char* what) {
 
 static int check_obs_width(lgs_sim* s, const char* what) {
     if (const int rc = check_obs_history(s, what)) return rc;
-    if (s->ohist.enabled) return LGS_OK;  // (the rows are frames of the head: checked above)
     if (!s->hobs.enabled) {
+        if (s->ohist.enabled) return LGS_OK;  // (the rows are frames of the head: checked above)
         if (s->task_obs > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS)
             return set_err(LGS_ERR_ARG, std::string(what) + ": obs counts exceed LGS_MAX_OBS (no height observations set)");
         return LGS_OK;
@@ -3720,10 +3732,12 @@ static int check_obs_width(lgs_sim* s, const char* what) {
         return set_err(LGS_ERR_ARG, std::string(what) + ": height observations need the quadruped or humanoid layout");
     const bool hum = s->task_layout == LGS_OBS_HUMANOID;
     const int head = hum ? 11 + 3 * A : 12 + 3 * A, head_priv = 14 + 3 * A;
-    if (head_priv > LGS_MAX_OBS || s->task_obs != head + P || (hum && s->task_priv != 0 && s->task_priv != head_priv + P) ||
+    const int frames = s->ohist.enabled ? s->ohist.frames : 1;  // (the privileged row has no history)
+    if (head_priv > LGS_MAX_OBS || s->task_obs != frames * head + P || (hum && s->task_priv != 0 && s->task_priv != head_priv + P) ||
         (!hum && s->task_priv > LGS_MAX_OBS))
         return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " / num_privileged_obs " +
-                       std::to_string(s->task_priv) + " do not match the layout's head (" + std::to_string(head) +
+                       std::to_string(s->task_priv) + " do not match " + (frames > 1 ? std::to_string(frames) + " frames of " : std::string()) +
+                       "the layout's head (" + std::to_string(head) +
                        (hum ? " / " + std::to_string(head_priv) : std::string()) + ") + " + std::to_string(P) + " scan points");
     return LGS_OK;
 }

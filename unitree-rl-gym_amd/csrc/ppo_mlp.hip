@@ -1419,7 +1419,8 @@ __global__ __launch_bounds__(64) void k_ppo_loss_step_reg(LossArgs a, LossStepOu
 // 16 rows per wave, NWV waves (threads past 64 NWV join the barriers only); the per-wave sums
 // are added in a fixed order into partial row `part`.  sh: LDS scratch of >= 96 + 19 NWV floats.
 // k_ppo_loss_step_q (NWV = 4, 64 rows per workgroup) and the update forward's epilogue
-// (k_mlp_fwd<96, .., LOSS>: NWV = 6, the workgroup's 96 rows) run it.
+// (k_mlp_fwd<96, .., LOSS>: NWV = 6, the workgroup's 96 rows; the WIDER form's 64 rows: NWV = 4)
+// run it.
 template <int NWV>
 __device__ __forceinline__ void loss_quad_rows(const LossArgs& a, const LossStepOut& o, int i0, int part, float* sh) {
     float* const c_h = sh;
@@ -1790,6 +1791,8 @@ __global__ __launch_bounds__(PMLP_OPT_THREADS) void k_adam_vec(float* __restrict
 #define FMLP_MAX_H0 512
 #define FMLP_MAX_H1 256
 #define FMLP_MAX_K0 256  // the input rows are staged in Y1 (row stride FMLP_MAX_H1 + 8)
+// past it, in whole groups of 4 k-steps: the WIDER forms, whose x region has Y0's row stride
+#define FMLP_MAX_K0_WIDER 512
 #define FMLP_THREADS 512
 
 struct FmlpJob {
@@ -1801,7 +1804,8 @@ struct FmlpJob {
     const bf16* W[4];       // W[l] = [N[l], K_l] bf16, ld K_l (K_0 = K0, K_l = N[l-1])
     const float* b[4];
     int N[4];
-    int K0;                 // padded input width, a multiple of 16, <= FMLP_MAX_K0
+    int K0;                 // padded input width: a multiple of 16, <= FMLP_MAX_K0, or a
+                            // multiple of 64, <= FMLP_MAX_K0_WIDER
     bf16* y[3];             // optional hidden outputs [M, N[l]] (ld ldy[l])
     int ldy[3];
     float* out;             // fp32 [M, N[3]] (ld ldo)
@@ -1816,7 +1820,8 @@ struct FmlpJobs {
 // One layer: D[R, N] = act(A[R, K] . W[N, K]^T + b), A in LDS (ld lda); wave w takes the
 // 32-column tiles w, w + 8, ...; every row tile of the workgroup per column tile, so a
 // B fragment (one 16-byte load per lane per k-step) feeds RT MFMAs.
-template <int R, bool LAST>
+// WHOLE: K is a multiple of 16 FG (whole groups of k-steps: no tail()).
+template <int R, bool LAST, bool WHOLE = false>
 __device__ __forceinline__ void fmlp_layer(const bf16* A, int lda, int K, const bf16* __restrict__ W,
                                            const bf16* __restrict__ Wf,
                                            const float* __restrict__ bias, int N, bf16* D, int ldd,
@@ -1894,7 +1899,9 @@ __device__ __forceinline__ void fmlp_layer(const bf16* A, int lda, int K, const 
             loadg(s0 + 2 * FG, bq);
             group(s0 + FG, bn);
         }
-        if (s0 < ks) {  // (ks not a multiple of 2 FG: the 48-wide input layer)
+        if constexpr (WHOLE) {
+            if (s0 < ks) group(s0, bq);  // (an odd count of groups: bq holds the last one)
+        } else if (s0 < ks) {  // (ks not a multiple of 2 FG: the 48-wide input layer)
             loadg(s0 + FG, bn);
             tail(s0, bq);
             tail(s0 + FG, bn);
@@ -2091,7 +2098,11 @@ __device__ void roll_epilogue(const FmlpJob& J, int jj, const RollStep& rs, int 
 // WIDE (the 96-row form at K0 > 64, which X cannot hold): x is staged in Y1 there too -- it is
 // dead once layer 0 has written Y0 -- and gathered again for a second job; the narrow
 // instantiations are the code they were
-template <int R, bool ROLL = false, bool LOSS = false, bool WIDE = false>
+// WIDER (256 < K0 <= 512, a multiple of 64): the region x and Y1 share takes Y0's row stride
+// (R * 520 bf16: 66,560 B of LDS in all at R = 32, two workgroups per CU; 133,120 B at R = 64,
+// the update's form, since 96 rows of Y0 leave 64,000 B, less than 96 rows of 448 inputs);
+// layer 0 runs whole groups of k-steps there.  Y1 keeps its own stride inside the region.
+template <int R, bool ROLL = false, bool LOSS = false, bool WIDE = false, bool WIDER = false>
 __global__ __launch_bounds__(FMLP_THREADS) void k_mlp_fwd(FmlpJobs jobs, int M, RollStep rs, LossArgs la = {},
                                                          LossStepOut lo = {}) {
     // y0 (then y2) and x (then y1); row strides 8 elements past the width: ds_read_b128
@@ -2100,13 +2111,14 @@ __global__ __launch_bounds__(FMLP_THREADS) void k_mlp_fwd(FmlpJobs jobs, int M, 
     // the 96-row form keeps input rows of up to 64 columns in a region of their own (LDX = 64 + 4:
     // the 160 KB hold it), so a second job on the same rows (the critic on the actor's observations)
     // does not gather them again; the 32-row form stages them in Y1 (3 workgroups per CU)
-    constexpr bool XR = R >= 96 && !WIDE;
+    constexpr bool XR = R >= 96 && !WIDE && !WIDER;
     constexpr int LDX = 68;
+    static_assert(!WIDER || (!WIDE && FMLP_MAX_K0_WIDER + 8 <= LD0 && R * LD0 * 4 <= 160 * 1024), "WIDER: x region");
     __shared__ __attribute__((aligned(16))) bf16 Y0[R * LD0];
-    __shared__ __attribute__((aligned(16))) bf16 Y1[R * LD1];
+    __shared__ __attribute__((aligned(16))) bf16 Y1[R * (WIDER ? LD0 : LD1)];
     __shared__ __attribute__((aligned(16))) bf16 X[XR ? R * LDX : 8];
     bf16* const xs = XR ? X : Y1;
-    const int ldxs = XR ? LDX : LD1;
+    const int ldxs = XR ? LDX : WIDER ? LD0 : LD1;
     const int r0 = blockIdx.x * R;
     const int jb = gridDim.y > 1 ? blockIdx.y : 0, je = gridDim.y > 1 ? blockIdx.y + 1 : jobs.njobs;
     for (int jj = jb; jj < je; ++jj) {
@@ -2139,7 +2151,12 @@ __global__ __launch_bounds__(FMLP_THREADS) void k_mlp_fwd(FmlpJobs jobs, int M, 
         }
         __syncthreads();
         FMLP_STAMP(sb + 1);
-        fmlp_layer<R, false>(xs, ldxs, J.K0, J.W[0], J.Wf[0], J.b[0], J.N[0], Y0, LD0, nullptr, 0, r0, M);
+        // (a narrower job beside a wider one, a 240-wide critic row beside a 320-wide actor row,
+        // takes the general loop: a uniform choice per job)
+        if (WIDER && J.K0 % 64 == 0)  // (WIDER is a template constant: the other forms keep one call)
+            fmlp_layer<R, false, WIDER>(xs, ldxs, J.K0, J.W[0], J.Wf[0], J.b[0], J.N[0], Y0, LD0, nullptr, 0, r0, M);
+        else
+            fmlp_layer<R, false>(xs, ldxs, J.K0, J.W[0], J.Wf[0], J.b[0], J.N[0], Y0, LD0, nullptr, 0, r0, M);
         FMLP_STAMP(sb + 2);
         __syncthreads();
         fmlp_store<R>(Y0, LD0, J.N[0], J.y[0], J.ldy[0], r0, M);
@@ -2957,8 +2974,8 @@ static int fmlp_pack(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, Fml
         const std::string w = "pmlp_mlp_forward job " + std::to_string(i) + ": ";
         if (!J.x || J.kx <= 0 || J.ldx < J.kx || (J.ldx % 4 == 0 && ((uintptr_t)J.x & 15)) || ((uintptr_t)J.x & 3))
             return fail(-1, w + "x: 0 < kx <= ldx, 16-byte aligned when ldx is a multiple of 4");
-        if (J.K0 <= 0 || J.K0 % 16 || J.K0 > FMLP_MAX_K0 || J.kx > J.K0)
-            return fail(-1, w + "K0 must be a multiple of 16, kx <= K0 <= 256");
+        if (J.K0 <= 0 || J.K0 % 16 || J.kx > J.K0 || (J.K0 > FMLP_MAX_K0 && J.K0 % 64) || J.K0 > FMLP_MAX_K0_WIDER)
+            return fail(-1, w + "K0 must be a multiple of 16, kx <= K0 <= 256, or a multiple of 64, kx <= K0 <= 512");
         if (J.xa && (J.ldxa < J.K0 || J.ldxa % 8 || !al16(J.xa))) return fail(-1, w + "xa: ldxa >= K0, a multiple of 8");
         const int lim[3] = {FMLP_MAX_H0, FMLP_MAX_H1, FMLP_MAX_H0};
         for (int l = 0; l < 4; ++l) {
@@ -2987,6 +3004,12 @@ static bool fmlp_wide(const FmlpJobs& fj) {
         if (fj.j[i].K0 > 64) return true;
     return false;
 }
+// a job's input rows are wider than Y1's rows: the WIDER forms (every job of the launch)
+static bool fmlp_wider(const FmlpJobs& fj) {
+    for (int i = 0; i < fj.njobs; ++i)
+        if (fj.j[i].K0 > FMLP_MAX_K0) return true;
+    return false;
+}
 
 PMLP_API int pmlp_mlp_forward(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32_t M, void* stream) {
     FmlpJobs fj;
@@ -2995,7 +3018,14 @@ PMLP_API int pmlp_mlp_forward(int32_t njobs, const pmlp_mlp_fwd_job* jobs, int32
     // mini-batches; 32 with one job per workgroup for the rollout's num_envs rows
     hipStream_t st = (hipStream_t)stream;
     const RollStep none{};
-    if (M >= 96 * 192 && fmlp_wide(fj))
+    if (fmlp_wider(fj)) {  // 64 rows (133 KB) for the update's mini-batches, 32 (two workgroups per CU) below
+        if (M >= 96 * 192)
+            hipLaunchKernelGGL((k_mlp_fwd<64, false, false, false, true>), dim3((M + 63) / 64, 1), dim3(FMLP_THREADS), 0,
+                               st, fj, M, none);
+        else
+            hipLaunchKernelGGL((k_mlp_fwd<32, false, false, false, true>), dim3((M + 31) / 32, njobs),
+                               dim3(FMLP_THREADS), 0, st, fj, M, none);
+    } else if (M >= 96 * 192 && fmlp_wide(fj))
         hipLaunchKernelGGL((k_mlp_fwd<96, false, false, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0, st, fj, M,
                            none);
     else if (M >= 96 * 192)
@@ -3028,8 +3058,12 @@ PMLP_API int pmlp_rollout_forward(const pmlp_mlp_fwd_job* jobs, int32_t N, const
                       r->st_mu, r->st_sigma, r->st_value, r->st_obs, r->st_cobs, r->draw, r->parity, r->seed,
                       r->rewards, r->dones, r->time_outs, r->prev_value, r->st_rewards, r->st_dones, r->gamma,
                       r->extras};
-    hipLaunchKernelGGL((k_mlp_fwd<32, true>), dim3((N + 31) / 32, 2), dim3(FMLP_THREADS), 0, (hipStream_t)stream,
-                       fj, N, rs);
+    if (fmlp_wider(fj)) {
+        hipLaunchKernelGGL((k_mlp_fwd<32, true, false, false, true>), dim3((N + 31) / 32, 2), dim3(FMLP_THREADS), 0,
+                           (hipStream_t)stream, fj, N, rs);
+    } else
+        hipLaunchKernelGGL((k_mlp_fwd<32, true>), dim3((N + 31) / 32, 2), dim3(FMLP_THREADS), 0, (hipStream_t)stream,
+                           fj, N, rs);
     PMLP_CHECK_LAUNCH("pmlp_rollout_forward");
     return 0;
 }
@@ -3171,6 +3205,11 @@ PMLP_API int pmlp_ppo_loss_step(const float* mu, const float* stdv, const float*
 PMLP_API int32_t pmlp_mlp_forward_ppo_loss_parts(int32_t M, int32_t A) {
     return (M >= 96 * 192 && A > 0 && A % 4 == 0 && A <= 16) ? ((M + 95) / 96) * (3 + A) : 0;
 }
+// with a job of K0 > 256 the workgroups own 64 rows (pmlp_ppo_loss_step_parts' count)
+PMLP_API int32_t pmlp_mlp_forward_ppo_loss_parts_k0(int32_t M, int32_t A, int32_t K0) {
+    const int32_t parts = pmlp_mlp_forward_ppo_loss_parts(M, A);
+    return parts > 0 && K0 > FMLP_MAX_K0 ? ((M + 63) / 64) * (3 + A) : parts;
+}
 
 PMLP_API int pmlp_mlp_forward_ppo_loss(const pmlp_mlp_fwd_job* jobs, int32_t M, const float* stdv,
                                        const float* actions, const float* old_logp, const float* old_mu,
@@ -3193,7 +3232,10 @@ PMLP_API int pmlp_mlp_forward_ppo_loss(const pmlp_mlp_fwd_job* jobs, int32_t M, 
         return fail(-1, "pmlp_mlp_forward_ppo_loss: null output or padded width too small");
     LossStepOut o{partial, (bf16*)dmu, (bf16*)dmu_t, (bf16*)dvalue, (bf16*)dvalue_t, Ap, Vp, nullptr, nullptr};
     const RollStep none{};
-    if (fmlp_wide(fj))
+    if (fmlp_wider(fj)) {
+        hipLaunchKernelGGL((k_mlp_fwd<64, false, true, false, true>), dim3((M + 63) / 64, 1), dim3(FMLP_THREADS), 0,
+                           (hipStream_t)stream, fj, M, none, a, o);
+    } else if (fmlp_wide(fj))
         hipLaunchKernelGGL((k_mlp_fwd<96, false, true, true>), dim3((M + 95) / 96, 1), dim3(FMLP_THREADS), 0,
                            (hipStream_t)stream, fj, M, none, a, o);
     else

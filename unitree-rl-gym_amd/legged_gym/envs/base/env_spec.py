@@ -99,6 +99,13 @@ def derive_env_spec(cfg, model, sim_dt, obs_layout, hip_dof_indices=(), verbose=
 def noise_scale_vec(cfg, num_obs, A, obs_layout):
     # an observation history (env.history_length = H > 1): the frame's vector, tiled
     H = int(getattr(cfg.env, "history_length", 1))
+    # with the height scan observed too: the head tiled, then the one scan's entries
+    P = 0
+    if getattr(cfg.terrain, "scan_in_observations", False) and obs_layout != cabi.OBS_HANDSTAND:
+        P = len(cfg.terrain.measured_points_x) * len(cfg.terrain.measured_points_y)
+    if H > 1 and P and num_obs > P and (num_obs - P) % H == 0:
+        v = _frame_noise_scale_vec(cfg, (num_obs - P) // H + P, A, obs_layout)
+        return np.concatenate([np.tile(v[:len(v) - P], H), v[len(v) - P:]])
     if H > 1 and num_obs % H == 0:
         return np.tile(_frame_noise_scale_vec(cfg, num_obs // H, A, obs_layout), H)
     return _frame_noise_scale_vec(cfg, num_obs, A, obs_layout)

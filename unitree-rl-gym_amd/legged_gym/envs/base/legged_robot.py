@@ -511,7 +511,9 @@ class LeggedRobot(BaseTask):
         kernel's own state (the newest H - 1 frames of the last row, obs_buf[:, F:]; read and
         written in place every step, editing it between steps is supported), _obs_history_fill
         [N] its per-env flag (0: the env's next row repeats its frame in every slot, as after a
-        reset); None when off.  num_obs_frame = F, the layout's own row width."""
+        reset); None when off.  num_obs_frame = F, the layout's own row width.  With
+        terrain.scan_in_observations the one current scan follows the frames: the row
+        is H * F + P wide, obs_history is obs_buf[:, F : H * F], and the scan is never stored."""
         self.obs_history_params = obs_history_params(self)
         self.obs_history = self._obs_history_fill = None
         R = self.obs_history_params

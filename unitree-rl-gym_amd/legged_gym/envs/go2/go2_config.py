@@ -83,6 +83,23 @@ class GO2RobustHistoryCfg(GO2RobustCfg):
         num_observations = 240
 
 
+class GO2TerrainRobustCfg(GO2TerrainCfg):
+    """go2_terrain_robust: the usual sim-to-real recipe in one task: go2_terrain's
+    rough terrain and height scan, go2_robust's actuator randomisation and action latency, and
+    the last 5 proprioceptive frames in front of the one current scan (5 x 48 + 187 = 427 policy
+    inputs: a history of the head alone, the scan never stored)."""
+
+    class env(GO2TerrainCfg.env):
+        history_length = 5
+        num_observations = 427
+
+    class domain_rand(GO2TerrainCfg.domain_rand):
+        randomize_kp = True
+        randomize_kd = True
+        randomize_motor_strength = True
+        randomize_action_delay = True
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -105,3 +122,8 @@ class GO2RobustCfgPPO(GO2RoughCfgPPO):
 class GO2RobustHistoryCfgPPO(GO2RobustCfgPPO):
     class runner(GO2RobustCfgPPO.runner):
         experiment_name = "go2_robust_history"
+
+
+class GO2TerrainRobustCfgPPO(GO2TerrainCfgPPO):
+    class runner(GO2TerrainCfgPPO.runner):
+        experiment_name = "go2_terrain_robust"

@@ -58,8 +58,10 @@ def build_task_params(env) -> cabi.TaskParams:
     # (with the height scan observed the vector's tail is the scan's one scale, in lgs_height_obs:
     # height_obs_params, which also refuses a cfg the tail cannot honour)
     # (with an observation history it is the newest frame's head: history_noise_head)
+    # (with both, DESIGN 3.13: the head tiled, then the scan's entries)
     hist = obs_history_params(env)
     if hist.enabled:
+        height_obs_params(env)  # (refuses a tail that is not one scale)
         _put(T.noise_vec, history_noise_head(env, hist))
     else:
         _put(T.noise_vec, _np(env.noise_scale_vec).reshape(-1)[:env.num_obs - height_obs_params(env).num_points])
@@ -174,9 +176,18 @@ def layout_head(obs_layout, A):
     raise ValueError("terrain.scan_in_observations needs the quadruped or the humanoid observation layout")
 
 
+def _history_length(cfg):
+    """cfg.env.history_length as a frame count, 1 where it is absent or not a valid count (the
+    value itself is refused by obs_history_params)."""
+    H = getattr(cfg.env, "history_length", 1)
+    ok = not isinstance(H, bool) and isinstance(H, (int, float)) and int(H) == H and 1 <= H <= cabi.MAX_OBS_FRAMES
+    return int(H) if ok else 1
+
+
 def check_scan_observations(cfg, obs_layout, A):
     """The constructor's checks of terrain.scan_in_observations: the layout, the grid's size and
-    cfg.env.num_observations / num_privileged_obs = the layout's head + the scan's points.
+    cfg.env.num_observations / num_privileged_obs = the layout's head + the scan's points; with
+    env.history_length = H > 1 the policy row is H heads, then the scan's points.
     Returns the number of scan points in the rows (0: the switch is off)."""
     if not scan_in_observations(cfg):
         return 0
@@ -185,7 +196,12 @@ def check_scan_observations(cfg, obs_layout, A):
     P = len(tc.measured_points_x) * len(tc.measured_points_y)
     if not 1 <= P <= cabi.MAX_SCAN_OBS:
         raise ValueError(f"terrain.scan_in_observations: {P} scan points, the rows take 1 to {cabi.MAX_SCAN_OBS}")
-    if cfg.env.num_observations != head + P:
+    H = _history_length(cfg)
+    if H > 1 and cfg.env.num_observations != H * head + P:
+        raise ValueError(f"env.history_length = {H} and terrain.scan_in_observations do not combine at "
+                         f"env.num_observations = {cfg.env.num_observations}: the row is {H} x the layout's {head} "
+                         f"+ {P} scan points, so it must be {H * head + P}")
+    if cfg.env.num_observations != H * head + P:
         raise ValueError(f"terrain.scan_in_observations: env.num_observations must be {head} + {P} scan points = "
                          f"{head + P}, not {cfg.env.num_observations}")
     priv = cfg.env.num_privileged_obs
@@ -262,8 +278,9 @@ def obs_history_params(env) -> cabi.ObsHistory:
     """lgs_obs_history of an env's cfg.env.history_length, without its buffers (the env
     allocates them when `enabled`).  1 is off.  With H >= 2 the policy row is the last H frames,
     oldest first, each the layout's own row; `num_frame` (not a field of the C struct) is that
-    row's width.  Refused: a length outside 1 .. 8, num_observations that is not H frames, the
-    height scan in the rows (the two do not combine yet), and a task class with a Python
+    row's width.  With terrain.scan_in_observations the row is those H frames, then
+    the one current scan: H * F + P entries.  Refused: a length outside 1 .. 8, num_observations
+    that is not H frames (+ the scan's points), and a task class with a Python
     compute_observations (it would edit a row whose older frames the kernel has already stored)."""
     R = cabi.ObsHistory()
     R.num_frame = 0
@@ -275,12 +292,16 @@ def obs_history_params(env) -> cabi.ObsHistory:
     if H == 1:
         return R
     F = obs_frame_width(env.obs_layout, env.num_actions, len(_np(env.feet_indices).reshape(-1)))
-    if env.cfg.env.num_observations != H * F:
+    if scan_in_observations(env.cfg):
+        tc = env.cfg.terrain
+        P = len(tc.measured_points_x) * len(tc.measured_points_y)
+        if env.cfg.env.num_observations != H * F + P:
+            raise ValueError(f"env.history_length = {H} and terrain.scan_in_observations do not combine at "
+                             f"env.num_observations = {env.cfg.env.num_observations}: the row is {H} x the layout's "
+                             f"{F} + {P} scan points, so it must be {H * F + P}")
+    elif env.cfg.env.num_observations != H * F:
         raise ValueError(f"env.history_length = {H}: env.num_observations must be {H} x the layout's {F} = "
                          f"{H * F}, not {env.cfg.env.num_observations}")
-    if scan_in_observations(env.cfg):
-        raise ValueError("env.history_length > 1 and terrain.scan_in_observations do not combine: a history "
-                         "of rows with the height scan is wider than every policy kernel")
     if "compute_observations" in getattr(env, "_hooks", frozenset()):
         raise ValueError("env.history_length > 1 with a Python compute_observations: the override would edit "
                          "a row whose older frames the kernel has already stored (INTEGRATION.md)")
@@ -291,10 +312,12 @@ def obs_history_params(env) -> cabi.ObsHistory:
 def history_noise_head(env, R):
     """The one frame's noise scales of env.noise_scale_vec under an observation history R: the
     vector is that head tiled R.frames times (older frames are copied, never re-noised, so the
-    kernel reads the head alone); an override that is not that tiling is refused."""
+    kernel reads the head alone); an override that is not that tiling is refused.  With the
+    height scan observed the scan's entries follow the tiling (height_obs_params reads them)."""
     v = _np(env.noise_scale_vec).astype(np.float32).reshape(-1)
     F, H = R.num_frame, R.frames
-    if len(v) != H * F or not (v.reshape(H, F) == v[:F]).all():
+    P = check_scan_observations(env.cfg, env.obs_layout, env.num_actions)
+    if len(v) != H * F + P or not (v[:H * F].reshape(H, F) == v[:F]).all():
         raise ValueError(f"_get_noise_scale_vec: with env.history_length = {H} the vector must be the frame's "
                          f"{F} scales tiled {H} times (the kernel noises the newest frame only)")
     return v[:F]

@@ -111,7 +111,7 @@ class FusedPPOStep:
         M, dev, bf = self.M, self.dev, torch.bfloat16
         L = len(self.lins[0])
         self.L = L
-        self.k0p = [_ceil8(ls[0].in_features) for ls in self.lins]
+        self.k0p = [mm._pad_k0(ls[0].in_features) for ls in self.lins]
         # row-major activations of exactly the layer's width (rows of 512 / 256 / 128 features
         # start on 128-byte lines); the weight gradients read them through LDS-transposed MFMA
         # operands (PARTIAL_TN: no transposed copy is ever written) and form the bias gradient
@@ -188,9 +188,11 @@ class FusedPPOStep:
             self.norm_partial = torch.empty(int(nparts), device=dev)
         self.nparts = 0
         # the loss in the forward's launch (pmlp_mlp_forward_ppo_loss: 96-row partials, fewer
-        # than pmlp_ppo_loss_step's 64-row ones, so loss_partial holds them) where it applies
+        # than pmlp_ppo_loss_step's 64-row ones, so loss_partial holds them; 64-row ones with a
+        # first layer wider than 256, the same count) where it applies
         lib = mm.load()
-        fl_parts = lib.pmlp_mlp_forward_ppo_loss_parts(M, A) if hasattr(lib, "pmlp_mlp_forward_ppo_loss") else 0
+        fl_parts = lib.pmlp_mlp_forward_ppo_loss_parts_k0(M, A, max(self.k0p)) \
+            if hasattr(lib, "pmlp_mlp_forward_ppo_loss") else 0
         Ap = self.dz_out[0].shape[1]
         self.fused_loss = bool(self.fused_fwd and self.fold_loss and 0 < fl_parts <= self.loss_partial.numel()
                                and Ap <= 16 and Ap % 4 == 0 and os.environ.get("PMLP_FUSED_LOSS", "1") != "0")

@@ -163,6 +163,8 @@ def load():
         if hasattr(L, "pmlp_mlp_forward_ppo_loss"):  # (absent from builds before round 4's end)
             L.pmlp_mlp_forward_ppo_loss_parts.argtypes = [i32, i32]
             L.pmlp_mlp_forward_ppo_loss_parts.restype = i32
+            L.pmlp_mlp_forward_ppo_loss_parts_k0.argtypes = [i32, i32, i32]
+            L.pmlp_mlp_forward_ppo_loss_parts_k0.restype = i32
             L.pmlp_mlp_forward_ppo_loss.argtypes = [C.POINTER(MlpFwdJob), i32] + [vp] * 9 + \
                 [i32, f32, i32, f32, f32, vp, vp, vp, i32, vp, vp, i32, vp]
         L.pmlp_rollout_forward.argtypes = [C.POINTER(MlpFwdJob), i32, C.POINTER(RolloutStep), vp]
@@ -189,6 +191,12 @@ def _ceil8(n):
     return (n + 7) // 8 * 8
 
 
+def _pad_k0(n):
+    """The first layer's padded input width: to 8 up to 256, to 64 above (pmlp_mlp_forward takes
+    multiples of 16 up to 256 and multiples of 64 up to 512; the zero columns add exact zeros)."""
+    return _ceil8(n) if n <= 256 else (n + 63) // 64 * 64
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -210,8 +218,9 @@ def supported(seq):
 
 def mlp_forward_supported(lins, k0p):
     """pmlp_mlp_forward's shape limits (include/ppo_mlp.h): 4 Linear layers, K0 a multiple
-    of 16 (<= 256), hidden widths multiples of 32 (<= 512 / 256 / 512), output <= 32."""
-    if len(lins) != 4 or k0p % 16 or k0p > 256:
+    of 16 (<= 256) or of 64 (<= 512), hidden widths multiples of 32 (<= 512 / 256 / 512),
+    output <= 32."""
+    if len(lins) != 4 or k0p % 16 or (k0p > 256 and k0p % 64) or k0p > 512:
         return False
     lim = (512, 256, 512)
     return all(lins[l].out_features % 32 == 0 and lins[l].out_features <= lim[l] for l in range(3)) and \
@@ -389,7 +398,7 @@ class _MfmaMLPsFn(torch.autograd.Function):
         M = xs[0].shape[0]
         assert all(x.shape[0] == M for x in xs)
         dev, bf = xs[0].device, torch.bfloat16
-        k0p = [_ceil8(x.shape[1]) for x in xs]
+        k0p = [_pad_k0(x.shape[1]) for x in xs]
         xb = [torch.empty(M, k0p[n], dtype=bf, device=dev) for n in range(nnets)]
         xt = [torch.empty(k0p[n], M, dtype=bf, device=dev) if train else None for n in range(nnets)]
         wb = [[torch.empty(W.shape[0], k0p[n] if l == 0 else W.shape[1], dtype=bf, device=dev)
