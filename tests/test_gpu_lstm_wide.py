@@ -3,6 +3,7 @@ observation row with the height scan): the input projection against fp64, the se
 kernels against the torch recurrence, the rollout step against the dense forward, and the
 fused recurrent update, the rollout and the runner on g1_terrain_scan's 234 / 237 rows."""
 import copy
+import os
 
 import numpy as np
 import pytest
@@ -166,6 +167,37 @@ def test_wide_step_is_bitwise_the_dense_forward_at_one_step():
             assert torch.equal(hs[n], h_in[n]) and torch.equal(cs[n], c_in[n])
             assert torch.equal(h[n][0], dense[n]["h_out"][0]) and torch.equal(c[n][0], dense[n]["c_out"][0])
             assert bool((h[n] != h_in[n]).any())
+
+
+@pytest.mark.skipif("PMLP_LSTM_STEP_TILES" in os.environ, reason="the tile count under test is overridden")
+@pytest.mark.parametrize("B", [4117, 8213])
+def test_wide_step_tile_loop_is_bitwise_the_one_tile_forward(B):
+    """The sequence kernel's tile loop with a ragged last tile, gx-fed form (234 / 237 inputs side
+    by side): B = 4117 is 2 tiles per workgroup, the last workgroup's second tile with 5 live
+    envs; B = 8213 is 4, the last workgroup running one full tile, one with 5 live envs, then
+    leaving the loop.  One in-place step (pmlp_lstm_step_wide_jobs with h_save / c_save) leaves
+    h, c bit for bit h_out[0] / c_out[0] of the dense forward (pmlp_lstm_fwd_wide_jobs at T = 1:
+    one tile per workgroup) from the same state, and saves the state it started from."""
+    torch.manual_seed(B)
+    Is = (234, 237)
+    L, st = lstm_seq._lib(), mm._stream()
+    rnns = [torch.nn.LSTM(i, H).cuda() for i in Is]
+    xs = [torch.randn(B, i, device="cuda") for i in Is]
+    h = [0.5 * torch.randn(1, B, H, device="cuda") for _ in Is]
+    c = [0.5 * torch.randn(1, B, H, device="cuda") for _ in Is]
+    h_in, c_in = [t.clone() for t in h], [t.clone() for t in c]
+    hs = [torch.full((1, B, H), float("nan"), device="cuda") for _ in Is]
+    cs = [torch.full((1, B, H), float("nan"), device="cuda") for _ in Is]
+    gx = [torch.empty(B, 4 * H, device="cuda") for _ in Is]
+    made = [_fwd_job(rnns[n], xs[n], h_in[n], c_in[n], 1, B) for n in range(2)]
+    jobs = (lstm_seq.LstmWideJob * 2)(*[m[0] for m in made])
+    lstm_seq._ok(L.pmlp_lstm_fwd_wide_jobs(2, jobs, 1, B, H, None, st), "fwd_wide")
+    lstm_seq.lstm_step_wide_pair_([(rnns[n], xs[n], h[n], c[n], (hs[n], cs[n]), gx[n]) for n in range(2)])
+    for n in range(2):
+        dense = made[n][1]
+        assert torch.equal(hs[n], h_in[n]) and torch.equal(cs[n], c_in[n])
+        assert bool(torch.isfinite(dense["h_out"]).all()) and bool((h[n] != h_in[n]).any())
+        assert torch.equal(h[n][0], dense["h_out"][0]) and torch.equal(c[n][0], dense["c_out"][0])
 
 
 O, P, A = 234, 237, 12  # g1_terrain_scan's rows: 47 / 50 + the 187-point height scan

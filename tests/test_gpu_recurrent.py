@@ -3,6 +3,7 @@ ActorCriticRecurrent, LSTM 64): the HIP sequence kernels (csrc/lstm_seq.hip) aga
 one recurrent PPO update at H1_2 scale against the same update in fp32 on the CPU (rsl_rl's
 padded-trajectory form), and the captured rollout/update graphs against eager."""
 import copy
+import os
 
 import numpy as np
 import pytest
@@ -478,6 +479,38 @@ def test_lstm_rollout_step_mfma_in_place_matches_nn_lstm():
         assert torch.equal(hs, h_ref) and torch.equal(cs, c_ref)
         torch.testing.assert_close(h, h_new, rtol=2e-5, atol=2e-5)
         torch.testing.assert_close(c, c_new, rtol=2e-5, atol=2e-5)
+
+
+@pytest.mark.skipif("PMLP_LSTM_STEP_TILES" in os.environ, reason="the tile count under test is overridden")
+@pytest.mark.parametrize("B", [4117, 8213])
+def test_lstm_step_mfma_tile_loop_is_bitwise_the_one_tile_forward(B):
+    """The sequence kernel's tile loop (several 16-env tiles per workgroup, the next tile's inputs
+    prefetched) with a ragged last tile: B = 4117 is 2 tiles per workgroup, the last workgroup's
+    second tile with 5 live envs; B = 8213 is 4, the last workgroup running one full tile, one
+    with 5 live envs, then leaving the loop.  One in-place step (pmlp_lstm_step_mfma_jobs, I = 47,
+    with h_save / c_save) leaves h, c bit for bit h_out[0] / c_out[0] of the dense forward
+    (pmlp_lstm_fwd_mfma_jobs at T = 1: one tile per workgroup) from the same state, and saves
+    the state it started from."""
+    from rsl_rl.modules import mfma_mlp as mm
+    torch.manual_seed(B)
+    I, H = 47, 64
+    L, P, st = lstm_seq._lib(), mm._p, mm._stream()
+    rnn = torch.nn.LSTM(I, H).cuda()
+    w = [t.detach().contiguous() for t in (rnn.weight_ih_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, rnn.weight_hh_l0)]
+    x = torch.randn(B, I, device="cuda")
+    h, c = 0.5 * torch.randn(B, H, device="cuda"), 0.5 * torch.randn(B, H, device="cuda")
+    h_in, c_in = h.clone(), c.clone()
+    f = lambda *s: torch.full(s, float("nan"), device="cuda")  # noqa: E731
+    h_out, c_out, gact, xh, hs, cs = f(1, B, H), f(1, B, H), f(1, B, 4 * H), f(1, B, I + H + 1), f(B, H), f(B, H)
+    dense = lstm_seq.LstmJob(I, P(x), P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(h_in), P(c_in), P(h_out), P(c_out),
+                             P(gact), P(xh), None, None, None, None)
+    lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(1, dense, 1, B, H, None, st), "fwd_mfma_jobs")
+    step = lstm_seq.LstmJob(I, P(x), P(w[0]), P(w[1]), P(w[2]), P(w[3]), None, None, P(h), P(c), None, None, None,
+                            None, P(hs), P(cs))
+    lstm_seq._ok(L.pmlp_lstm_step_mfma_jobs(1, step, B, H, st), "step_mfma_jobs")
+    assert torch.equal(hs, h_in) and torch.equal(cs, c_in)
+    assert bool(torch.isfinite(h_out).all()) and bool((h != h_in).any())
+    assert torch.equal(h, h_out[0]) and torch.equal(c, c_out[0])
 
 
 @pytest.mark.parametrize("done_dtype", [torch.bool, torch.int64])

@@ -9,7 +9,9 @@ import os
 import statistics
 import sys
 
-KERNELS = ("k_lstm_fwd_mfma8", "k_lstm_bwd_mfma", "k_heads_fwd", "k_heads_bwd")
+# (k_lstm_fwd8<false> / <true>: the sequence kernel's x-fed and gx-fed forms, once
+# k_lstm_fwd_mfma8 and k_lstm_fwd_gx8)
+KERNELS = ("k_lstm_fwd8<false>", "k_lstm_fwd8<true>", "k_lstm_bwd_mfma", "k_heads_fwd", "k_heads_bwd")
 
 
 def load(path):

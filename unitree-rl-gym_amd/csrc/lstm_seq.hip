@@ -361,8 +361,9 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bwd(int T, int B, const float* _
 // envs are ONE [16 x 128] . [128 x 256] product, [x_t | h_{t-1}] . [W_ih | W_hh]^T, on
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulation from the fp32 bias.  Precision: every
 // operand is split into bf16 hi + lo (v = hi + lo to ~2^-16 relative) and the product is
-// hi.hi + hi.lo + lo.hi (SPLIT = 3), near fp32 (SPLIT = 1, the plain bf16 product, was 5e-2
-// off on the pretrained policies' action means: not shipped).
+// hi.hi + hi.lo + lo.hi, near fp32.  (The kernels once had a SPLIT parameter whose other value,
+// 1, was the plain bf16 product: it was 5e-2 off on the pretrained policies' action means, was
+// never shipped, and is gone.)
 // The cell update, c and h stay in the lanes (fp32); the weight fragments are loaded once;
 // h_{t-1} and x_t sit in a double-buffered LDS operand, one barrier per step.  Outputs as
 // k_lstm_fwd (fp32).
@@ -371,6 +372,7 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bwd(int T, int B, const float* _
 // wave w is exactly the lane's own (env, unit) pairs.
 constexpr int ME = 16, MH = 64, MG = 256, MKX = 64;  // envs per workgroup, hidden, gates, x slots
 constexpr int MLDA = MKX + MH + 8;                   // LDS row stride of [x | h] (bf16): 272 B
+constexpr int MLDH = MH + 8;                         // LDS row stride of h alone (bf16): 144 B
 constexpr int MLDG = MG + 8;                         // LDS row stride of dG (bf16): 528 B
 
 typedef __bf16 mbf16;
@@ -395,8 +397,19 @@ struct MFwdArgs {
     float *h_save, *c_save;  // optional: the state the sequence starts from (the rollout's storage slot)
 };
 
+// The gx-fed form's (wide inputs, below): the input projection ran beforehand, gx [T, B, 256]
+// already holds x W_ih^T + b_ih + b_hh
+struct WFwdArgs {
+    int T, B;
+    const float *gx, *whh, *h0, *c0;
+    const uint8_t* reset;
+    float *h_out, *c_out, *gact;
+    float* hp;               // optional: [h_prev | 1] rows [T, B, 65], the backward's operand
+    float *h_save, *c_save;  // optional, as MFwdArgs
+};
+
 // Eight waves (512 threads, two waves per SIMD): wave w owns units 8w .. 8w + 7 as two
-// 16-column tiles, [i | f] and [g | o] (8 units each), so a step is 24 MFMAs per wave (a
+// 16-column tiles, [i | f] and [g | o] (8 units each), so a step is 24 MFMAs per wave (12 in the gx-fed form; a
 // 4-wave form with the four gate tiles of 16 units per wave ran 68 vs 59 us at H1 scale).
 // A lane (column j) holds i, g (j < 8) or f, o (j >= 8) of unit 8w + (j & 7) for its 4 rows;
 // the partner lane j ^ 8 (DPP row_ror:8, one VALU move per value) supplies the other two
@@ -409,16 +422,47 @@ __device__ __forceinline__ float ror8(float v) {
 // 2,048-env mini-batch is 128 workgroups, half the CUs, so one launch of both fills them):
 // blockIdx.y selects the job; a job with fewer workgroups than the grid's x leaves the rest.
 struct MFwdBatch { MFwdArgs m[2]; };
+struct WFwdBatch { WFwdArgs m[2]; };
+
+// The sequence kernel has two forms, and this is all that differs between them:
+//   x-fed  (I <= 64): K = [x | h], 4 k-steps of 32 over LDS rows of MLDA, h at column MKX; the
+//     fragments hold [W_ih | W_hh] rows; the accumulators start from b_ih + b_hh; the first 256
+//     threads stage x, 4 floats each per step (16 envs x 64 slots); the backward's operand row is
+//     xh = [x | h_prev | 1];
+//   gx-fed (wide inputs): K = the 64 h columns, 2 k-steps over rows of MLDH; the fragments hold
+//     W_hh alone; the accumulators start from the env's gx row (8 floats per lane and step);
+//     the operand row is hp = [h_prev | 1] (the x-fed row at I = 0).
+template <bool GX> struct Fwd8;
+template <> struct Fwd8<false> {
+    using Args = MFwdArgs;
+    using Batch = MFwdBatch;
+    // LDS row stride, h column, k-steps, 4-float groups of input per lane and step
+    static constexpr int LD = MLDA, HO = MKX, KS = 4, NI = 1;
+    static __device__ __forceinline__ int inputs(const Args& a) { return a.I; }
+    static __device__ __forceinline__ const float* in(const Args& a) { return a.x; }
+    static __device__ __forceinline__ float* operand(const Args& a) { return a.xh; }
+};
+template <> struct Fwd8<true> {
+    using Args = WFwdArgs;
+    using Batch = WFwdBatch;
+    static constexpr int LD = MLDH, HO = 0, KS = 2, NI = 2;
+    static __device__ __forceinline__ int inputs(const Args&) { return 0; }
+    static __device__ __forceinline__ const float* in(const Args& a) { return a.gx; }
+    static __device__ __forceinline__ float* operand(const Args& a) { return a.hp; }
+};
 
 // tiles: consecutive 16-env tiles per workgroup, run one after the other on the weight
 // fragments loaded once (the rollout's single steps: the fragments' 128 KB of loads per
 // workgroup otherwise dominate a T = 1 launch); each tile's arithmetic is the same
-template <int SPLIT>
-__global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles) {
-    constexpr int NP = SPLIT == 3 ? 2 : 1;  // operand parts (hi, lo)
-    __shared__ __attribute__((aligned(16))) mbf16 A[NP][2][ME * MLDA];
-    const MFwdArgs a = ab.m[blockIdx.y];
-    const int T = a.T, B = a.B, I = a.I, RL = I + MH + 1;
+template <bool GX>
+__global__ __launch_bounds__(512) void k_lstm_fwd8(typename Fwd8<GX>::Batch ab, int tiles) {
+    using F = Fwd8<GX>;
+    constexpr int LD = F::LD, HO = F::HO, KS = F::KS, NI = F::NI;
+    __shared__ __attribute__((aligned(16))) mbf16 A[2][2][ME * LD];  // [hi, lo][buffer]
+    const typename F::Args a = ab.m[blockIdx.y];
+    const int T = a.T, B = a.B, I = F::inputs(a), RL = I + MH + 1;
+    const float* const in = F::in(a);  // x [T, B, I] / gx [T, B, 256]
+    float* const orow = F::operand(a);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int ebase = blockIdx.x * ME * tiles;
     if (ebase >= B) return;  // (whole workgroup)
@@ -426,36 +470,58 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
     const int hj = j >> 3;                    // 0: this column holds i / g, 1: f / o
     const int uu = 8 * w + (j & 7);           // this lane's unit
     // weight fragments: tile t (0: [i | f], 1: [g | o]), k-step s
-    mbf16x8 wf[NP][2][4];
-    float bias[2];
+    mbf16x8 wf[2][2][KS];
+    int gr[2];      // the lane's gate row per tile (gx-fed: its gx column)
+    float bias[2];  // (x-fed)
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
         const int r = (2 * tt + hj) * MH + uu;
-        bias[tt] = a.bih[r] + a.bhh[r];
+        gr[tt] = r;
+        if constexpr (!GX) bias[tt] = a.bih[r] + a.bhh[r];
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+        for (int s = 0; s < KS; ++s)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int k = s * 32 + 8 * rg + e;
-                const float v = k < MKX ? (k < I ? a.wih[(size_t)r * I + k] : 0.f) : a.whh[(size_t)r * MH + (k - MKX)];
+                float v;
+                if constexpr (GX) v = a.whh[(size_t)r * MH + s * 32 + 8 * rg + e];
+                else v = k < MKX ? (k < I ? a.wih[(size_t)r * I + k] : 0.f) : a.whh[(size_t)r * MH + (k - MKX)];
                 mbf16 hi, lo;
                 split_bf16(v, hi, lo);
                 wf[0][tt][s][e] = hi;
-                if constexpr (NP == 2) wf[NP - 1][tt][s][e] = lo;
+                wf[1][tt][s][e] = lo;
             }
     }
-    // a tile's t = 0 inputs (state, reset, x), loaded for tile q + 1 while tile q computes (the
-    // rollout's multi-tile steps: each tile otherwise waits one full round trip on them);
-    // unconditional loads at clamped addresses, masked where used
-    const bool xs = tid < 256;
+    // step t's input values of the lane, unconditional loads at clamped addresses (past T - 1
+    // and B - 1: loaded, never used).  x-fed: 4 x slots of env xe (the staging threads');
+    // gx-fed: the gx values of its accumulators, rows 4 rg .. 4 rg + 3 of both tiles
+    const bool xs = GX || tid < 256;
     const int xe = (tid & 255) >> 4, xk = (tid & 15) * 4;
-    float pf_h[2], pf_c[2], pf_x[4];
+    auto trow = [&](int t) { return (size_t)min(t, T - 1) * B; };  // step t's first row, clamped
+    auto iload = [&](int e0n, size_t tc, float (&dst)[NI][4]) {
+        if constexpr (GX) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const float* row = in + (tc + min(e0n + 4 * rg + p, B - 1)) * MG;
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) dst[tt][p] = row[gr[tt]];
+            }
+        } else {
+            const int gc = min(e0n + xe, B - 1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[0][i] = in[(tc + gc) * I + min(xk + i, I - 1)];
+        }
+    };
+    // a tile's t = 0 inputs (state, reset, x / gx), loaded for tile q + 1 while tile q computes
+    // (the rollout's multi-tile steps: each tile otherwise waits one full round trip on them);
+    // unconditional loads at clamped addresses, masked where used
+    float pf_h[2], pf_c[2], pf_i[NI][4];
     uint8_t pf_r[2], pf_rn[2];  // resets at t = 0 and at t = 1 (rload(1))
-    const uint8_t* rbase = a.reset ? a.reset : (const uint8_t*)a.x;  // masked when absent
-    // (absent h0 / c0 / reset: a load of x[0], masked -- no branch, which would put a vmcnt(0)
+    const uint8_t* rbase = a.reset ? a.reset : (const uint8_t*)in;  // masked when absent
+    // (absent h0 / c0 / reset: a load of in[0], masked -- no branch, which would put a vmcnt(0)
     // behind every load)
-    const float* h0p = a.h0 ? a.h0 : a.x;
-    const float* c0p = a.c0 ? a.c0 : a.x;
+    const float* h0p = a.h0 ? a.h0 : in;
+    const float* c0p = a.c0 ? a.c0 : in;
     auto in_load = [&](int e0n) {
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
@@ -468,44 +534,41 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
             pf_r[pp] = a.reset ? r0 : (uint8_t)0;
             pf_rn[pp] = rbase[(size_t)min(1, T - 1) * B + gc];
         }
-        const int gx = min(e0n + xe, B - 1);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pf_x[i] = a.x[(size_t)gx * I + min(xk + i, I - 1)];
+        // (row 0 either way, T >= 1: each form keeps the address arithmetic it was measured with,
+        // and the [NI][4] shape of the input registers likewise -- as one flat array of 8 the
+        // gx-fed step loop was scheduled differently)
+        iload(e0n, GX ? trow(0) : 0, pf_i);
     };
     in_load(ebase);
     for (int q = 0; q < tiles; ++q) {
     const int e0 = ebase + q * ME;
-    if (e0 >= B) break;   // (uniform)
+    if (e0 >= B) break;      // (uniform)
     if (q) __syncthreads();  // the previous tile's last reads of A are done
     auto put = [&](int buf, int idx, float v) {  // operand element (hi, lo)
         mbf16 hi, lo;
         split_bf16(v, hi, lo);
         A[0][buf][idx] = hi;
-        if constexpr (NP == 2) A[NP - 1][buf][idx] = lo;
+        A[1][buf][idx] = lo;
     };
-    // x staging by the first 256 threads: 4 floats each per step (16 envs x 64 slots).  x and
-    // the resets are loaded two steps ahead (xr: step t + 1's, stored at the end of step t; xr2:
-    // step t + 2's): vmcnt counts the per-step stores too and retires in order, so a load issued
+    // The inputs and the resets are loaded two steps ahead (inx: step t + 1's, in2: step t + 2's;
+    // x-fed: inx goes to LDS at the end of step t; gx-fed: gcur, step t's, starts the
+    // accumulators): vmcnt counts the per-step stores too and retires in order, so a load issued
     // after step t's stores and used one step later waited for those stores as well
-    float xr[4], xr2[4];
-    auto xload = [&](int t, float (&dst)[4]) {
-        const int gc = min(e0 + xe, B - 1);
-        const size_t tc = (size_t)min(t, T - 1);
+    float gcur[NI][4], inx[NI][4], in2[NI][4];
+    auto xstore = [&](int buf, int t) {  // (x-fed) x_t into the operand and the xh row
+        if constexpr (!GX) {
+            const int ge = e0 + xe;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dst[i] = a.x[(tc * B + gc) * I + min(xk + i, I - 1)];
-    };
-    auto xstore = [&](int buf, int t) {
-        const int ge = e0 + xe;
+            for (int i = 0; i < 4; ++i) inx[0][i] = (ge < B && xk + i < I) ? inx[0][i] : 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xr[i] = (ge < B && xk + i < I) ? xr[i] : 0.f;
+            for (int i = 0; i < 4; ++i) put(buf, xe * LD + xk + i, inx[0][i]);
+            if (orow && ge < B) {
+                float* row = orow + ((size_t)t * B + ge) * RL;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) put(buf, xe * MLDA + xk + i, xr[i]);
-        if (a.xh && ge < B) {
-            float* row = a.xh + ((size_t)t * B + ge) * RL;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (xk + i < I) row[xk + i] = xr[i];
-            if (xk == 0) row[I + MH] = 1.f;
+                for (int i = 0; i < 4; ++i)
+                    if (xk + i < I) row[xk + i] = inx[0][i];
+                if (xk == 0) row[I + MH] = 1.f;
+            }
         }
     };
     // state of the lane's 2 (env, unit) pairs: rows 2 hj, 2 hj + 1 of its row group
@@ -518,7 +581,7 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
         const float c0 = ge < B ? pf_c[pp] : 0.f;
         hp[pp] = rs ? 0.f : h0;
         c[pp] = rs ? 0.f : c0;
-        put(0, (4 * rg + p) * MLDA + MKX + uu, hp[pp]);
+        put(0, (4 * rg + p) * LD + HO + uu, hp[pp]);
         if (a.h_save && ge < B) {
             a.h_save[(size_t)ge * MH + uu] = hp[pp];
             a.c_save[(size_t)ge * MH + uu] = c[pp];
@@ -526,7 +589,7 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
     }
     const bool has_reset = a.reset != nullptr;
     auto rload = [&](int t, uint8_t* r) {
-        const size_t tc = (size_t)min(t, T - 1) * B;
+        const size_t tc = trow(t);
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) r[pp] = rbase[tc + min(e0 + 4 * rg + 2 * hj + pp, B - 1)];
     };
@@ -535,9 +598,11 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
     rload(2, rnx2);
     if (xs) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) xr[i] = pf_x[i];  // (xload(0), prefetched)
+        for (int tt = 0; tt < NI; ++tt)
+#pragma unroll
+            for (int p = 0; p < 4; ++p) (GX ? gcur : inx)[tt][p] = pf_i[tt][p];  // (iload(0), prefetched)
         xstore(0, 0);
-        if (T > 1) xload(1, xr);
+        if (GX || T > 1) iload(e0, trow(1), inx);
     }
     // the next tile's, in flight from here (not hoisted above this tile's last uses of the
     // prefetched values: vmcnt is in order, so those would then wait for these)
@@ -553,25 +618,26 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
             rnx[pp] = rnx2[pp];
         }
         rload(t + 3, rnx2);
-        if (xs) xload(t + 2, xr2);  // (clamped to T - 1 past the end)
+        if (xs) iload(e0, trow(t + 2), in2);  // (clamped to T - 1 past the end)
         mfloatx4 acc[2];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-            for (int p = 0; p < 4; ++p) acc[tt][p] = bias[tt];
+            for (int p = 0; p < 4; ++p) {
+                if constexpr (GX) acc[tt][p] = gcur[tt][p];
+                else acc[tt][p] = bias[tt];
+            }
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int o = j * MLDA + s * 32 + 8 * rg;
+        for (int s = 0; s < KS; ++s) {
+            const int o = j * LD + s * 32 + 8 * rg;
             const mbf16x8 ah = *(const mbf16x8*)(&A[0][cur][o]);
+            const mbf16x8 al = *(const mbf16x8*)(&A[1][cur][o]);
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[0][tt][s], acc[tt], 0, 0, 0);
-            if constexpr (NP == 2) {
-                const mbf16x8 al = *(const mbf16x8*)(&A[NP - 1][cur][o]);
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[NP - 1][tt][s], acc[tt], 0, 0, 0);
+            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[1][tt][s], acc[tt], 0, 0, 0);
 #pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][tt][s], acc[tt], 0, 0, 0);
-            }
+            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][tt][s], acc[tt], 0, 0, 0);
         }
         // own rows and the partner's: own = rows 2 hj + pp, sent = the partner's own rows
         float ownA[2], ownB[2], rcvA[2], rcvB[2];
@@ -594,21 +660,30 @@ __global__ __launch_bounds__(512) void k_lstm_fwd_mfma8(MFwdBatch ab, int tiles)
             if (ge < B) {
                 const size_t row = (size_t)t * B + ge;
                 if (a.gact) {
-                    float* gr = a.gact + row * MG;
-                    gr[uu] = ig; gr[MH + uu] = fg; gr[2 * MH + uu] = gg; gr[3 * MH + uu] = og;
+                    float* ga = a.gact + row * MG;
+                    ga[uu] = ig; ga[MH + uu] = fg; ga[2 * MH + uu] = gg; ga[3 * MH + uu] = og;
                 }
                 if (a.c_out) a.c_out[row * MH + uu] = cn;
                 if (a.h_out) a.h_out[row * MH + uu] = hn;
-                if (a.xh) a.xh[row * RL + I + uu] = hp[pp];  // the state this step started from
+                if (orow) {
+                    orow[row * RL + I + uu] = hp[pp];  // the state this step started from
+                    if constexpr (GX)                  // (x-fed: the 1 goes with the x entries)
+                        if (uu == 0) orow[row * RL + MH] = 1.f;
+                }
             }
             c[pp] = rn[pp] ? 0.f : cn;  // a reset at t + 1 starts that step from zero
             hp[pp] = rn[pp] ? 0.f : hn;
-            if (t + 1 < T) put(nxt, (4 * rg + p) * MLDA + MKX + uu, hp[pp]);
+            if (t + 1 < T) put(nxt, (4 * rg + p) * LD + HO + uu, hp[pp]);
         }
         if (xs) {
             if (t + 1 < T) xstore(nxt, t + 1);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xr[i] = xr2[i];
+            for (int tt = 0; tt < NI; ++tt)
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    if constexpr (GX) gcur[tt][p] = inx[tt][p];
+                    inx[tt][p] = in2[tt][p];
+                }
         }
         __syncthreads();
     }
@@ -638,16 +713,15 @@ typedef float mfloatx16 __attribute__((ext_vector_type(16)));
 
 struct MBwdBatch { MBwdArgs m[2]; };  // as MFwdBatch
 
-template <int SPLIT, bool DW>
+template <bool DW>
 __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) {
-    constexpr int NP = SPLIT == 3 ? 2 : 1;
     const MBwdArgs a = ab.m[blockIdx.y];
     if ((int)blockIdx.x * ME >= a.B) return;  // (whole workgroup)
-    __shared__ __attribute__((aligned(16))) mbf16 G[NP][2][ME * MLDG];
+    __shared__ __attribute__((aligned(16))) mbf16 G[2][2][ME * MLDG];
     // DW operands, transposed so a fragment is 8 consecutive envs (one 16-byte read):
     // GT[perm gate col][env], XT[xh col][env]
-    __shared__ __attribute__((aligned(16))) mbf16 GT[DW ? NP : 1][2][DW ? MG * ME : 8];
-    __shared__ __attribute__((aligned(16))) mbf16 XT[DW ? NP : 1][2][DW ? MXC * ME : 8];
+    __shared__ __attribute__((aligned(16))) mbf16 GT[DW ? 2 : 1][2][DW ? MG * ME : 8];
+    __shared__ __attribute__((aligned(16))) mbf16 XT[DW ? 2 : 1][2][DW ? MXC * ME : 8];
     const int T = a.T, B = a.B;
     const int e0 = blockIdx.x * ME;
     if (DW && threadIdx.x >= 256) {
@@ -676,7 +750,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
             // columns >= RL stay 0.  Only those: columns < RL are written by the step stores below
             // from other waves, with no barrier between (a zero landing after one of them would
             // drop that column of the first step's operand)
-            for (int i = wt; i < NP * 2 * MXC * ME; i += 256)
+            for (int i = wt; i < 2 * 2 * MXC * ME; i += 256)
                 if ((i % (MXC * ME)) / ME >= RL) (&XT[0][0][0])[i] = (mbf16)0.f;
             xload(T - 1, xr);
             xload(T - 2, xr2);
@@ -692,7 +766,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
                         lo8[k] = lo;
                     }
                     *(mbf16x8*)(&XT[0][buf][xc * ME + 8 * xg]) = hi8;
-                    if constexpr (NP == 2) *(mbf16x8*)(&XT[NP - 1][buf][xc * ME + 8 * xg]) = lo8;
+                    *(mbf16x8*)(&XT[1][buf][xc * ME + 8 * xg]) = lo8;
                 }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) xr[k] = xr2[k];
@@ -705,16 +779,16 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
                 for (int mt = 0; mt < 2; ++mt) {
                     const int ao = ((2 * ww + mt) * 32 + (lane & 31)) * ME + 8 * (lane >> 5);
                     ah[mt] = *(const mbf16x8*)(&GT[0][buf][ao]);
-                    if constexpr (NP == 2) al[mt] = *(const mbf16x8*)(&GT[NP - 1][buf][ao]);
+                    al[mt] = *(const mbf16x8*)(&GT[1][buf][ao]);
                 }
 #pragma unroll
                 for (int nt = 0; nt < MXC / 32; ++nt) {
                     const int bo = (nt * 32 + (lane & 31)) * ME + 8 * (lane >> 5);
                     bh[nt] = *(const mbf16x8*)(&XT[0][buf][bo]);
-                    if constexpr (NP == 2) bl[nt] = *(const mbf16x8*)(&XT[NP - 1][buf][bo]);
+                    bl[nt] = *(const mbf16x8*)(&XT[1][buf][bo]);
                 }
 #pragma unroll
-                for (int pass = 0; pass < (NP == 2 ? 3 : 1); ++pass)
+                for (int pass = 0; pass < 3; ++pass)
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -751,7 +825,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int j = lane & 15, rg = lane >> 4, u = 16 * w + j;
     // B[k = permuted gate column][n = unit 16w + j] = W_hh[torch row of k][u], 8 k-steps of 32
-    mbf16x8 wf[NP][8];
+    mbf16x8 wf[2][8];
 #pragma unroll
     for (int s = 0; s < 8; ++s)
 #pragma unroll
@@ -761,7 +835,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
             mbf16 hi, lo;
             split_bf16(a.whh[(size_t)(kq * MH + 16 * kw + kj) * MH + u], hi, lo);
             wf[0][s][e] = hi;
-            if constexpr (NP == 2) wf[NP - 1][s][e] = lo;
+            wf[1][s][e] = lo;
         }
     // the step's global inputs for the lane's 4 (env, unit) pairs, loaded one step ahead
     struct In {
@@ -831,7 +905,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
                 split_bf16(dg[q], hi, lo);
                 const int o = (4 * rg + p) * MLDG + 64 * w + 16 * q + j;
                 G[0][buf][o] = hi;
-                if constexpr (NP == 2) G[NP - 1][buf][o] = lo;
+                G[1][buf][o] = lo;
                 if constexpr (DW) {
                     gth[q][p] = hi;
                     gtl[q][p] = lo;
@@ -843,7 +917,7 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
             for (int q = 0; q < 4; ++q) {
                 const int ot = (64 * w + 16 * q + j) * ME + 4 * rg;
                 *(mbf16x4*)(&GT[0][buf][ot]) = gth[q];
-                if constexpr (NP == 2) *(mbf16x4*)(&GT[NP - 1][buf][ot]) = gtl[q];
+                *(mbf16x4*)(&GT[1][buf][ot]) = gtl[q];
             }
         }
         __syncthreads();
@@ -861,11 +935,9 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
             const int o = j * MLDG + s * 32 + 8 * rg;
             const mbf16x8 ah = *(const mbf16x8*)(&G[0][buf][o]);
             acc[s & 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[0][s], acc[s & 1][0], 0, 0, 0);
-            if constexpr (NP == 2) {
-                const mbf16x8 al = *(const mbf16x8*)(&G[NP - 1][buf][o]);
-                acc[s & 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[NP - 1][s], acc[s & 1][1], 0, 0, 0);
-                acc[s & 1][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][s], acc[s & 1][2], 0, 0, 0);
-            }
+            const mbf16x8 al = *(const mbf16x8*)(&G[1][buf][o]);
+            acc[s & 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[1][s], acc[s & 1][1], 0, 0, 0);
+            acc[s & 1][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][s], acc[s & 1][2], 0, 0, 0);
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -877,18 +949,17 @@ __global__ __launch_bounds__(DW ? 512 : 256) void k_lstm_bwd_mfma(MBwdBatch ab) 
 
 // -------------------------------------------------------------- wide inputs --
 // Inputs of 65 .. 384 columns (an observation row with the height scan): W_ih no longer fits
-// the lanes (k_lstm_fwd_mfma8's wf would be ~160 VGPRs at I = 240) nor LDS (245 KB as bf16
+// the lanes (the x-fed k_lstm_fwd8's wf would be ~160 VGPRs at I = 240) nor LDS (245 KB as bf16
 // hi + lo), and the input projection has no recurrence in it, so it runs beforehand as one
-// product over all T B rows (k_lstm_proj_wide -> gx); the sequence kernel (k_lstm_fwd_gx8)
-// starts each step's accumulators from the env's gx row instead of the bias and keeps only
-// the 64 h columns as K.  The backward is k_lstm_bwd_mfma<3, true> on the x-less operand
+// product over all T B rows (k_lstm_proj_wide -> gx); the sequence kernel's gx-fed form
+// (k_lstm_fwd8<true>) starts each step's accumulators from the env's gx row instead of the bias
+// and keeps only the 64 h columns as K.  The backward is k_lstm_bwd_mfma<true> on the x-less operand
 // [h_prev | 1] (I = 0, RL = 65: dW_hh and db in its slabs) writing dgx, and dW_ih = dGx^T X
 // is one more product over the rows (k_lstm_dwih_wide).  Every product is the split-bf16
 // form above (hi.hi + hi.lo + lo.hi, fp32 accumulation).
 constexpr int WI_MIN = MKX + 1, WI_MAX = 384;  // input widths of the wide form
 constexpr int PM = 64, PK = 32;                // projection: rows per workgroup, k-chunk
 constexpr int PLD = PK + 8;                    // LDS row stride of a k-chunk (bf16): 80 B
-constexpr int MLDH = MH + 8;                   // LDS row stride of h (bf16): 144 B
 constexpr int WDR = 512, WDC = 128;            // dW_ih: rows and x columns per workgroup
 
 struct WProjArgs {
@@ -914,7 +985,7 @@ __global__ __launch_bounds__(256) void k_lstm_proj_wide(WProjBatch ab) {
     const int l32 = lane & 31, lh = lane >> 5;
     const int kk = tid & 31, rr = tid >> 5;  // staging: column kk of rows rr, rr + 8, ..
     float xv[PM / 8], wv[MG / 8];
-    // unconditional loads at clamped addresses, masked where stored (see k_lstm_fwd_mfma8)
+    // unconditional loads at clamped addresses, masked where stored (see k_lstm_fwd8)
     auto load = [&](int k0) {
         const int kc = min(k0 + kk, I - 1);
 #pragma unroll
@@ -986,190 +1057,6 @@ __global__ __launch_bounds__(256) void k_lstm_proj_wide(WProjBatch ab) {
                 const int row = r0 + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (row < M) a.gx[(size_t)row * MG + 64 * w + 32 * nt + l32] = acc[mt][nt][r];
             }
-}
-
-struct WFwdArgs {
-    int T, B;
-    const float *gx, *whh, *h0, *c0;
-    const uint8_t* reset;
-    float *h_out, *c_out, *gact;
-    float* hp;               // optional: [h_prev | 1] rows [T, B, 65], the backward's operand
-    float *h_save, *c_save;  // optional, as MFwdArgs
-};
-struct WFwdBatch { WFwdArgs m[2]; };
-
-// k_lstm_fwd_mfma8's recurrence (its lane layout, gate arithmetic, resets, tiles and two-step
-// prefetch) with K = the 64 h columns, 2 k-steps per step, and the accumulators started from the
-// env's gx row (8 floats per lane and step, loaded two steps ahead) instead of the bias.
-__global__ __launch_bounds__(512) void k_lstm_fwd_gx8(WFwdBatch ab, int tiles) {
-    __shared__ __attribute__((aligned(16))) mbf16 A[2][2][ME * MLDH];  // [hi, lo][buffer]
-    const WFwdArgs a = ab.m[blockIdx.y];
-    const int T = a.T, B = a.B, RL = MH + 1;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int ebase = blockIdx.x * ME * tiles;
-    if (ebase >= B) return;  // (whole workgroup)
-    const int j = lane & 15, rg = lane >> 4, hj = j >> 3, uu = 8 * w + (j & 7);
-    mbf16x8 wf[2][2][2];  // [hi, lo][tile][k-step]
-    int gr[2];            // the lane's gate row (gx column) per tile
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        gr[tt] = (2 * tt + hj) * MH + uu;
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                mbf16 hi, lo;
-                split_bf16(a.whh[(size_t)gr[tt] * MH + s * 32 + 8 * rg + e], hi, lo);
-                wf[0][tt][s][e] = hi;
-                wf[1][tt][s][e] = lo;
-            }
-    }
-    // the gx values of the lane's accumulators at step t: rows 4 rg .. 4 rg + 3, both tiles
-    // (clamped past T - 1 and B - 1: loaded, never used)
-    auto gload = [&](int e0n, int t, float (&dst)[2][4]) {
-        const size_t tc = (size_t)min(t, T - 1) * B;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const float* row = a.gx + (tc + min(e0n + 4 * rg + p, B - 1)) * MG;
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) dst[tt][p] = row[gr[tt]];
-        }
-    };
-    float pf_h[2], pf_c[2], pf_g[2][4];
-    uint8_t pf_r[2], pf_rn[2];
-    const uint8_t* rbase = a.reset ? a.reset : (const uint8_t*)a.gx;  // masked when absent
-    const float* h0p = a.h0 ? a.h0 : a.gx;
-    const float* c0p = a.c0 ? a.c0 : a.gx;
-    auto in_load = [&](int e0n) {
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            const int gc = min(e0n + 4 * rg + 2 * hj + pp, B - 1);
-            const float hv = h0p[a.h0 ? (size_t)gc * MH + uu : 0];
-            const float cv = c0p[a.c0 ? (size_t)gc * MH + uu : 0];
-            const uint8_t r0 = rbase[a.reset ? gc : 0];
-            pf_h[pp] = a.h0 ? hv : 0.f;
-            pf_c[pp] = a.c0 ? cv : 0.f;
-            pf_r[pp] = a.reset ? r0 : (uint8_t)0;
-            pf_rn[pp] = rbase[(size_t)min(1, T - 1) * B + gc];
-        }
-        gload(e0n, 0, pf_g);
-    };
-    in_load(ebase);
-    for (int q = 0; q < tiles; ++q) {
-    const int e0 = ebase + q * ME;
-    if (e0 >= B) break;      // (uniform)
-    if (q) __syncthreads();  // the previous tile's last reads of A are done
-    auto put = [&](int buf, int idx, float v) {
-        mbf16 hi, lo;
-        split_bf16(v, hi, lo);
-        A[0][buf][idx] = hi;
-        A[1][buf][idx] = lo;
-    };
-    float c[2], hp[2];
-#pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-        const int p = 2 * hj + pp, ge = e0 + 4 * rg + p;
-        const bool rs = a.reset && ge < B && pf_r[pp];
-        const float h0 = ge < B ? pf_h[pp] : 0.f;
-        const float c0 = ge < B ? pf_c[pp] : 0.f;
-        hp[pp] = rs ? 0.f : h0;
-        c[pp] = rs ? 0.f : c0;
-        put(0, (4 * rg + p) * MLDH + uu, hp[pp]);
-        if (a.h_save && ge < B) {
-            a.h_save[(size_t)ge * MH + uu] = hp[pp];
-            a.c_save[(size_t)ge * MH + uu] = c[pp];
-        }
-    }
-    const bool has_reset = a.reset != nullptr;
-    auto rload = [&](int t, uint8_t* r) {
-        const size_t tc = (size_t)min(t, T - 1) * B;
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) r[pp] = rbase[tc + min(e0 + 4 * rg + 2 * hj + pp, B - 1)];
-    };
-    uint8_t rnx[2] = {pf_rn[0], pf_rn[1]};  // reset(t + 1) at step t
-    uint8_t rnx2[2];                          // reset(t + 2)
-    rload(2, rnx2);
-    float gcur[2][4], gnx[2][4], gn2[2][4];  // gx of steps t, t + 1, t + 2
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int p = 0; p < 4; ++p) gcur[tt][p] = pf_g[tt][p];
-    gload(e0, 1, gnx);
-    // the next tile's inputs, in flight from here (see k_lstm_fwd_mfma8)
-    __builtin_amdgcn_sched_barrier(0);
-    if (q + 1 < tiles && e0 + ME < B) in_load(e0 + ME);
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-        const int cur = t & 1;
-        bool rn[2];
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            rn[pp] = has_reset && t + 1 < T && rnx[pp] != 0;
-            rnx[pp] = rnx2[pp];
-        }
-        rload(t + 3, rnx2);
-        gload(e0, t + 2, gn2);
-        mfloatx4 acc[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int p = 0; p < 4; ++p) acc[tt][p] = gcur[tt][p];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int o = j * MLDH + s * 32 + 8 * rg;
-            const mbf16x8 ah = *(const mbf16x8*)(&A[0][cur][o]);
-            const mbf16x8 al = *(const mbf16x8*)(&A[1][cur][o]);
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[0][tt][s], acc[tt], 0, 0, 0);
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wf[1][tt][s], acc[tt], 0, 0, 0);
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wf[0][tt][s], acc[tt], 0, 0, 0);
-        }
-        float ownA[2], ownB[2], rcvA[2], rcvB[2];
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            ownA[pp] = hj ? acc[0][2 + pp] : acc[0][pp];
-            ownB[pp] = hj ? acc[1][2 + pp] : acc[1][pp];
-            rcvA[pp] = ror8(hj ? acc[0][pp] : acc[0][2 + pp]);
-            rcvB[pp] = ror8(hj ? acc[1][pp] : acc[1][2 + pp]);
-        }
-        const int nxt = cur ^ 1;
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            const int p = 2 * hj + pp, ge = e0 + 4 * rg + p;
-            const float zi = hj ? rcvA[pp] : ownA[pp], zf = hj ? ownA[pp] : rcvA[pp];
-            const float zg = hj ? rcvB[pp] : ownB[pp], zo = hj ? ownB[pp] : rcvB[pp];
-            const float ig = fsig(zi), fg = fsig(zf), gg = ftanh(zg), og = fsig(zo);
-            const float cn = fg * c[pp] + ig * gg;
-            const float hn = og * ftanh(cn);
-            if (ge < B) {
-                const size_t row = (size_t)t * B + ge;
-                if (a.gact) {
-                    float* ga = a.gact + row * MG;
-                    ga[uu] = ig; ga[MH + uu] = fg; ga[2 * MH + uu] = gg; ga[3 * MH + uu] = og;
-                }
-                if (a.c_out) a.c_out[row * MH + uu] = cn;
-                if (a.h_out) a.h_out[row * MH + uu] = hn;
-                if (a.hp) {
-                    a.hp[row * RL + uu] = hp[pp];  // the state this step started from
-                    if (uu == 0) a.hp[row * RL + MH] = 1.f;
-                }
-            }
-            c[pp] = rn[pp] ? 0.f : cn;  // a reset at t + 1 starts that step from zero
-            hp[pp] = rn[pp] ? 0.f : hn;
-            if (t + 1 < T) put(nxt, (4 * rg + p) * MLDH + uu, hp[pp]);
-        }
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                gcur[tt][p] = gnx[tt][p];
-                gnx[tt][p] = gn2[tt][p];
-            }
-        __syncthreads();
-    }
-    }  // tiles
 }
 
 struct WDwArgs {
@@ -1864,14 +1751,28 @@ int fail(const std::string& m) {
     return -1;
 }
 
+// after a launch: 0, or the launch's error under the entry point's name
+int launched(const char* what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The sequence kernel on njobs memories of B envs, `tiles` 16-env tiles per workgroup; pack(i)
+// gives job i's arguments.
+template <bool GX, typename Pack>
+void fwd8_launch(int njobs, int B, int tiles, hipStream_t s, Pack&& pack) {
+    typename Fwd8<GX>::Batch a{};
+    for (int i = 0; i < njobs; ++i) a.m[i] = pack(i);
+    hipLaunchKernelGGL(k_lstm_fwd8<GX>, dim3((B + ME * tiles - 1) / (ME * tiles), njobs), dim3(512), 0, s, a, tiles);
+}
+
 template <int H, int IP>
 int fwd_launch(const FwdArgs& a, hipStream_t s) {
     if ((a.B + EB_MAX - 1) / EB_MAX >= 512)
         hipLaunchKernelGGL((k_lstm_fwd<H, EB_MAX, IP>), dim3((a.B + EB_MAX - 1) / EB_MAX), dim3(4 * H), 0, s, a);
     else
         hipLaunchKernelGGL((k_lstm_fwd<H, 4, IP>), dim3((a.B + 3) / 4), dim3(4 * H), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_fwd: ") + hipGetErrorString(e));
+    return launched("pmlp_lstm_fwd");
 }
 
 template <int H>
@@ -1891,8 +1792,7 @@ int bwd_h(int T, int B, const float* whh, const float* c0, const uint8_t* reset,
     else
         hipLaunchKernelGGL((k_lstm_bwd<H, 4>), dim3((B + 3) / 4), dim3(4 * H), 0, s, T, B, whh, c0, reset, c_out, gact,
                            dh_out, dgx);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_bwd: ") + hipGetErrorString(e));
+    return launched("pmlp_lstm_bwd");
 }
 
 }  // namespace
@@ -1971,11 +1871,10 @@ PMLP_API int pmlp_lstm_fwd_mfma(int32_t T, int32_t B, int32_t H, int32_t I, cons
                                 const uint8_t* reset, float* h_out, float* c_out, float* gact, float* xh, void* stream) {
     if (T <= 0 || B <= 0 || !x || !wih || !bih || !bhh || !whh) return fail("pmlp_lstm_fwd_mfma: empty sequence or null input");
     if (H != MH || I <= 0 || I > MKX) return fail("pmlp_lstm_fwd_mfma: hidden 64, input 1..64");
-    MFwdBatch a{};
-    a.m[0] = MFwdArgs{T, B, I, x, wih, bih, bhh, whh, h0, c0, reset, h_out, c_out, gact, xh, nullptr, nullptr};
-    hipLaunchKernelGGL(k_lstm_fwd_mfma8<3>, dim3((B + ME - 1) / ME), dim3(512), 0, (hipStream_t)stream, a, 1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_fwd_mfma: ") + hipGetErrorString(e));
+    fwd8_launch<false>(1, B, 1, (hipStream_t)stream, [&](int) {
+        return MFwdArgs{T, B, I, x, wih, bih, bhh, whh, h0, c0, reset, h_out, c_out, gact, xh, nullptr, nullptr};
+    });
+    return launched("pmlp_lstm_fwd_mfma");
 }
 
 PMLP_API int pmlp_lstm_bwd_mfma(int32_t T, int32_t B, int32_t H, const float* whh, const float* c0,
@@ -1985,9 +1884,8 @@ PMLP_API int pmlp_lstm_bwd_mfma(int32_t T, int32_t B, int32_t H, const float* wh
     if (H != MH) return fail("pmlp_lstm_bwd_mfma: hidden 64");
     MBwdBatch a{};
     a.m[0] = MBwdArgs{T, B, whh, c0, reset, c_out, gact, dh_out, dgx, nullptr, 0, nullptr};
-    hipLaunchKernelGGL((k_lstm_bwd_mfma<3, false>), dim3((B + ME - 1) / ME), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_bwd_mfma: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL((k_lstm_bwd_mfma<false>), dim3((B + ME - 1) / ME), dim3(256), 0, (hipStream_t)stream, a);
+    return launched("pmlp_lstm_bwd_mfma");
 }
 
 PMLP_API int32_t pmlp_lstm_bwd_dw_blocks(int32_t B) { return (B + ME - 1) / ME; }
@@ -2000,9 +1898,8 @@ PMLP_API int pmlp_lstm_bwd_dw_mfma(int32_t T, int32_t B, int32_t H, int32_t I, c
     if (H != MH || I <= 0 || I + MH + 1 > MXC) return fail("pmlp_lstm_bwd_dw_mfma: hidden 64, I + 65 <= 128");
     MBwdBatch a{};
     a.m[0] = MBwdArgs{T, B, whh, c0, reset, c_out, gact, dh_out, nullptr, xh, I, slab};
-    hipLaunchKernelGGL((k_lstm_bwd_mfma<3, true>), dim3((B + ME - 1) / ME), dim3(512), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_bwd_dw_mfma: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL((k_lstm_bwd_mfma<true>), dim3((B + ME - 1) / ME), dim3(512), 0, (hipStream_t)stream, a);
+    return launched("pmlp_lstm_bwd_dw_mfma");
 }
 
 /* The recurrent policy's MLP heads (include/ppo_mlp.h, "recurrent heads"). */
@@ -2065,8 +1962,7 @@ PMLP_API int pmlp_heads_forward(int32_t njobs, const pmlp_head_job* jobs, int32_
     if (H == 32) heads_fwd_launch<32, false>(njobs, hj, M, HeadAct{}, s);
     else if (H == 64) heads_fwd_launch<64, false>(njobs, hj, M, HeadAct{}, s);
     else heads_fwd_launch<128, false>(njobs, hj, M, HeadAct{}, s);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_heads_forward: ") + hipGetErrorString(e));
+    return launched("pmlp_heads_forward");
 }
 
 PMLP_API int pmlp_heads_forward_act(const pmlp_head_job* jobs, int32_t M, int32_t H, const pmlp_head_act* act,
@@ -2084,8 +1980,7 @@ PMLP_API int pmlp_heads_forward_act(const pmlp_head_job* jobs, int32_t M, int32_
     if (H == 32) heads_fwd_launch<32, true>(2, hj, M, ha, s);
     else if (H == 64) heads_fwd_launch<64, true>(2, hj, M, ha, s);
     else heads_fwd_launch<128, true>(2, hj, M, ha, s);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_heads_forward_act: ") + hipGetErrorString(e));
+    return launched("pmlp_heads_forward_act");
 }
 
 PMLP_API int pmlp_heads_backward(int32_t njobs, const pmlp_head_job* jobs, int32_t M, int32_t H, void* stream) {
@@ -2098,8 +1993,7 @@ PMLP_API int pmlp_heads_backward(int32_t njobs, const pmlp_head_job* jobs, int32
     if (H == 32) hipLaunchKernelGGL(mf ? (k_heads_bwd<32, BR, true>) : (k_heads_bwd<32, BR>), g, dim3(2 * BR), 0, s, hj, M);
     else if (H == 64) hipLaunchKernelGGL(mf ? (k_heads_bwd<64, BR, true>) : (k_heads_bwd<64, BR>), g, dim3(2 * BR), 0, s, hj, M);
     else hipLaunchKernelGGL(mf ? (k_heads_bwd<128, BR, true>) : (k_heads_bwd<128, BR>), g, dim3(2 * BR), 0, s, hj, M);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_heads_backward: ") + hipGetErrorString(e));
+    return launched("pmlp_heads_backward");
 }
 
 /* One rollout step of a hidden-64 memory on the matrix cores (the 8-wave sequence kernel at
@@ -2112,12 +2006,10 @@ PMLP_API int pmlp_lstm_step_mfma(int32_t B, int32_t H, int32_t I, const float* x
     if (B <= 0 || !x || !wih || !bih || !bhh || !whh || !h || !c) return fail("pmlp_lstm_step_mfma: null input");
     if (H != MH || I <= 0 || I > MKX) return fail("pmlp_lstm_step_mfma: hidden 64, input 1..64");
     if ((h_save == nullptr) != (c_save == nullptr)) return fail("pmlp_lstm_step_mfma: h_save and c_save together");
-    MFwdBatch a{};
-    a.m[0] = MFwdArgs{1, B, I, x, wih, bih, bhh, whh, h, c, nullptr, h, c, nullptr, nullptr, h_save, c_save};
-    const int nt = step_tiles(B);
-    hipLaunchKernelGGL(k_lstm_fwd_mfma8<3>, dim3((B + ME * nt - 1) / (ME * nt)), dim3(512), 0, (hipStream_t)stream, a, nt);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_step_mfma: ") + hipGetErrorString(e));
+    fwd8_launch<false>(1, B, step_tiles(B), (hipStream_t)stream, [&](int) {
+        return MFwdArgs{1, B, I, x, wih, bih, bhh, whh, h, c, nullptr, h, c, nullptr, nullptr, h_save, c_save};
+    });
+    return launched("pmlp_lstm_step_mfma");
 }
 
 /* Both memories of the fused recurrent step in one launch each way (include/ppo_mlp.h,
@@ -2139,15 +2031,12 @@ static int lstm_jobs_check(const char* w, int njobs, const pmlp_lstm_job* jobs, 
 PMLP_API int pmlp_lstm_fwd_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t T, int32_t B, int32_t H,
                                      const uint8_t* reset, void* stream) {
     if (int e = lstm_jobs_check("pmlp_lstm_fwd_mfma_jobs", njobs, jobs, T, B, H, false)) return e;
-    MFwdBatch a{};
-    for (int i = 0; i < njobs; ++i) {
+    fwd8_launch<false>(njobs, B, 1, (hipStream_t)stream, [&](int i) {
         const pmlp_lstm_job& J = jobs[i];
-        a.m[i] = MFwdArgs{T, B, J.I, J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h0, J.c0, reset,
-                          J.h_out, J.c_out, J.gact, J.xh, nullptr, nullptr};
-    }
-    hipLaunchKernelGGL(k_lstm_fwd_mfma8<3>, dim3((B + ME - 1) / ME, njobs), dim3(512), 0, (hipStream_t)stream, a, 1);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_fwd_mfma_jobs: ") + hipGetErrorString(e));
+        return MFwdArgs{T, B, J.I, J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h0, J.c0, reset,
+                        J.h_out, J.c_out, J.gact, J.xh, nullptr, nullptr};
+    });
+    return launched("pmlp_lstm_fwd_mfma_jobs");
 }
 
 PMLP_API int pmlp_lstm_bwd_dw_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t T, int32_t B, int32_t H,
@@ -2158,27 +2047,25 @@ PMLP_API int pmlp_lstm_bwd_dw_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs
         const pmlp_lstm_job& J = jobs[i];
         a.m[i] = MBwdArgs{T, B, J.w_hh, J.c0, reset, J.c_out, J.gact, J.dh_out, nullptr, J.xh, J.I, J.slab};
     }
-    hipLaunchKernelGGL((k_lstm_bwd_mfma<3, true>), dim3((B + ME - 1) / ME, njobs), dim3(512), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_bwd_dw_mfma_jobs: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL((k_lstm_bwd_mfma<true>), dim3((B + ME - 1) / ME, njobs), dim3(512), 0, (hipStream_t)stream, a);
+    return launched("pmlp_lstm_bwd_dw_mfma_jobs");
 }
 
 PMLP_API int pmlp_lstm_step_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t B, int32_t H, void* stream) {
     if (njobs < 1 || njobs > 2 || !jobs || B <= 0) return fail("pmlp_lstm_step_mfma_jobs: 1..2 jobs, B > 0");
     if (H != MH) return fail("pmlp_lstm_step_mfma_jobs: hidden 64");
-    MFwdBatch a{};
     for (int i = 0; i < njobs; ++i) {
         const pmlp_lstm_job& J = jobs[i];
         if (J.I <= 0 || J.I > MKX || !J.x || !J.w_ih || !J.b_ih || !J.b_hh || !J.w_hh || !J.h_out || !J.c_out ||
             (J.h_save == nullptr) != (J.c_save == nullptr))
             return fail("pmlp_lstm_step_mfma_jobs: input 1..64, null input / state, h_save and c_save together");
-        a.m[i] = MFwdArgs{1, B, J.I, J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h_out, J.c_out, nullptr,
-                          J.h_out, J.c_out, nullptr, nullptr, J.h_save, J.c_save};
     }
-    const int nt = step_tiles(B);
-    hipLaunchKernelGGL(k_lstm_fwd_mfma8<3>, dim3((B + ME * nt - 1) / (ME * nt), njobs), dim3(512), 0, (hipStream_t)stream, a, nt);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string("pmlp_lstm_step_mfma_jobs: ") + hipGetErrorString(e));
+    fwd8_launch<false>(njobs, B, step_tiles(B), (hipStream_t)stream, [&](int i) {
+        const pmlp_lstm_job& J = jobs[i];
+        return MFwdArgs{1, B, J.I, J.x, J.w_ih, J.b_ih, J.b_hh, J.w_hh, J.h_out, J.c_out, nullptr,
+                        J.h_out, J.c_out, nullptr, nullptr, J.h_save, J.c_save};
+    });
+    return launched("pmlp_lstm_step_mfma_jobs");
 }
 
 /* Wide inputs (include/ppo_mlp.h, "wide inputs"): the input projection, the sequence from gx,
@@ -2218,11 +2105,6 @@ static int wide_check(const char* w, int njobs, const pmlp_lstm_wide_job* jobs, 
     return 0;
 }
 
-static int wide_launched(const char* w) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(std::string(w) + ": " + hipGetErrorString(e));
-}
-
 // gx of every job's M rows in one launch
 static void wide_proj(int njobs, const pmlp_lstm_wide_job* jobs, int M, hipStream_t s) {
     WProjBatch p{};
@@ -2236,14 +2118,12 @@ PMLP_API int pmlp_lstm_fwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jo
     if (int e = wide_check(w, njobs, jobs, T, B, H, WIDE_FWD)) return e;
     hipStream_t s = (hipStream_t)stream;
     wide_proj(njobs, jobs, T * B, s);
-    if (int e = wide_launched(w)) return e;
-    WFwdBatch a{};
-    for (int i = 0; i < njobs; ++i) {
+    if (int e = launched(w)) return e;
+    fwd8_launch<true>(njobs, B, 1, s, [&](int i) {
         const pmlp_lstm_wide_job& J = jobs[i];
-        a.m[i] = WFwdArgs{T, B, J.gx, J.w_hh, J.h0, J.c0, reset, J.h_out, J.c_out, J.gact, J.hp, nullptr, nullptr};
-    }
-    hipLaunchKernelGGL(k_lstm_fwd_gx8, dim3((B + ME - 1) / ME, njobs), dim3(512), 0, s, a, 1);
-    return wide_launched(w);
+        return WFwdArgs{T, B, J.gx, J.w_hh, J.h0, J.c0, reset, J.h_out, J.c_out, J.gact, J.hp, nullptr, nullptr};
+    });
+    return launched(w);
 }
 
 PMLP_API int pmlp_lstm_bwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t T, int32_t B, int32_t H,
@@ -2261,11 +2141,11 @@ PMLP_API int pmlp_lstm_bwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jo
         d.m[i] = WDwArgs{T * B, J.I, J.dgx, J.x, J.slab_ih};
         imax = std::max(imax, (int)J.I);
     }
-    hipLaunchKernelGGL((k_lstm_bwd_mfma<3, true>), dim3((B + ME - 1) / ME, njobs), dim3(512), 0, s, a);
-    if (int e = wide_launched(w)) return e;
+    hipLaunchKernelGGL((k_lstm_bwd_mfma<true>), dim3((B + ME - 1) / ME, njobs), dim3(512), 0, s, a);
+    if (int e = launched(w)) return e;
     hipLaunchKernelGGL(k_lstm_dwih_wide, dim3(pmlp_lstm_wide_dw_blocks(T, B), njobs, (imax + WDC - 1) / WDC), dim3(256),
                        0, s, d);
-    return wide_launched(w);
+    return launched(w);
 }
 
 PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t B, int32_t H,
@@ -2274,14 +2154,11 @@ PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* j
     if (int e = wide_check(w, njobs, jobs, 1, B, H, WIDE_STEP)) return e;
     hipStream_t s = (hipStream_t)stream;
     wide_proj(njobs, jobs, B, s);
-    if (int e = wide_launched(w)) return e;
-    WFwdBatch a{};
-    for (int i = 0; i < njobs; ++i) {
+    if (int e = launched(w)) return e;
+    fwd8_launch<true>(njobs, B, step_tiles(B), s, [&](int i) {
         const pmlp_lstm_wide_job& J = jobs[i];
-        a.m[i] = WFwdArgs{1, B, J.gx, J.w_hh, J.h_out, J.c_out, nullptr, J.h_out, J.c_out, nullptr, nullptr,
-                          J.h_save, J.c_save};
-    }
-    const int nt = step_tiles(B);
-    hipLaunchKernelGGL(k_lstm_fwd_gx8, dim3((B + ME * nt - 1) / (ME * nt), njobs), dim3(512), 0, s, a, nt);
-    return wide_launched(w);
+        return WFwdArgs{1, B, J.gx, J.w_hh, J.h_out, J.c_out, nullptr, J.h_out, J.c_out, nullptr, nullptr,
+                        J.h_save, J.c_save};
+    });
+    return launched(w);
 }
