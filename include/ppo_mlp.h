@@ -105,9 +105,12 @@ PMLP_API int pmlp_gemm(int32_t epi, int32_t njobs, const pmlp_gemm_job* jobs, in
  * those of the two launches. */
 PMLP_API int pmlp_gemm_pair(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
                             const pmlp_gemm_job* jobs_x, void* stream);
-/* operand staging of pmlp_gemm's k-loop: 1 (default; env PMLP_GLDS) = LDS-DMA into two LDS buffers,
- * one barrier per k-tile, wherever the shapes allow (whole 64-deep k-tiles); 0 = register staging.
- * Both compute the same MFMA chain (bitwise equal).  Returns the previous setting. */
+/* operand staging of pmlp_gemm's k-loop: 1 (the default; no environment variable is read) = LDS-DMA
+ * into two LDS buffers, one barrier per k-tile, wherever the shapes allow (whole 64-deep k-tiles);
+ * 0 = register staging; 2 = LDS-DMA only for PARTIAL_TN, as a ring of four buffers; 3 = that ring
+ * plus the two buffers for BWD_DX (2 and 3 exist for in-process comparisons; values outside 0..3
+ * are clamped).  Every mode computes the same MFMA chain (bitwise equal).  The setting is
+ * process-global.  Returns the previous setting. */
 PMLP_API int pmlp_set_gemm_staging(int32_t glds);
 
 /* out[i] = sum_s slab[s*stride + i], i < n (fp32): the split-K combine.
