@@ -584,4 +584,42 @@ PMLP_API int pmlp_lstm_bwd_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jo
 PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* jobs, int32_t B, int32_t H,
                                       void* stream);
 
+/* ---- recurrent memory: GRU.  rsl_rl v1.0.2 Memory with rnn_type="gru" (one-layer nn.GRU,
+ * gate order r, z, n) in the dense form of the LSTM above, on the matrix cores with the
+ * arithmetic of pmlp_lstm_fwd_mfma (split-bf16 products, fp32 accumulation from the fp32
+ * bias, fp32 state).  Hidden 64, inputs 1..64 (pmlp_gru_supported), fp32 tensors.
+ *   gi = x_t W_ih^T + b_ih, gh = h W_hh^T + b_hh, r = sig(gi_r + gh_r), z = sig(gi_z + gh_z),
+ *   n = tanh(gi_n + r gh_n), h = (1 - z) n + z h;  h is zeroed before step t where reset[t].
+ *   forward:  x [T,B,I], w_ih [192,I], b_ih, b_hh [192], w_hh [192,64], h0 [B,64] (NULL: zeros)
+ *             -> h_out [T,B,64]; gact [T,B,256] = [r | z | n | gh_n] and
+ *             xh [T,B,I+65] = [x | h_prev | 1] (h_prev: the state the step starts from, after a
+ *             reset), both optional: what the backward reads; h_save [B,64] (optional): the
+ *             state the sequence starts from
+ *   backward: w_hh, gact, xh, dh_out [T,B,64] -> dg [T,B,256] = [da_r | da_z | da_n | da_hn],
+ *             the gradients of the four pre-activations (a_n = gi_n + r gh_n, a_hn = gh_n); the
+ *             parameter gradients are products of dg and xh over the T*B rows: dW_ih, db_ih
+ *             from dg columns 0..191, dW_hh, db_hh from columns 0..127 and 192..255.  No
+ *             gradient flows into h0 or across a reset.
+ *   step:     one rollout step (T = 1) with h = h_out [B,64] read and overwritten in place,
+ *             h_save optional; the forward's kernel, so the step's h is the forward's h_out[0]
+ *             bit for bit.
+ * Each entry takes 1..2 jobs (side by side in the grid: the actor's and the critic's memory)
+ * over the same [T, B] and reset mask (NULL: no resets); every check runs before the launch
+ * (text in pmlp_lstm_last_error).                                                          */
+typedef struct pmlp_gru_job {
+    int32_t I;                                   /* input width, 1..64                    */
+    const float *x, *w_ih, *b_ih, *b_hh, *w_hh;  /* [T,B,I], torch nn.GRU parameters      */
+    const float* h0;                             /* [B,64] state the sequence starts from */
+    float *h_out, *gact, *xh;                    /* forward outputs (backward inputs)     */
+    const float* dh_out;                         /* backward: gradient of h_out [T,B,64]  */
+    float* dg;                                   /* backward: gate gradients [T,B,256]    */
+    float* h_save;                               /* the state the sequence starts from    */
+} pmlp_gru_job;
+PMLP_API int pmlp_gru_supported(int32_t hidden, int32_t input);
+PMLP_API int pmlp_gru_fwd_jobs(int32_t njobs, const pmlp_gru_job* jobs, int32_t T, int32_t B, int32_t H,
+                               const uint8_t* reset, void* stream);
+PMLP_API int pmlp_gru_bwd_jobs(int32_t njobs, const pmlp_gru_job* jobs, int32_t T, int32_t B, int32_t H,
+                               const uint8_t* reset, void* stream);
+PMLP_API int pmlp_gru_step_jobs(int32_t njobs, const pmlp_gru_job* jobs, int32_t B, int32_t H, void* stream);
+
 #endif

@@ -22,6 +22,7 @@
 
 #include "../../include/ppo_mlp.h"
 #include "pmlp_noise.h"
+#include "seq_mfma.h"
 
 namespace {
 
@@ -375,19 +376,7 @@ constexpr int MLDA = MKX + MH + 8;                   // LDS row stride of [x | h
 constexpr int MLDH = MH + 8;                         // LDS row stride of h alone (bf16): 144 B
 constexpr int MLDG = MG + 8;                         // LDS row stride of dG (bf16): 528 B
 
-typedef __bf16 mbf16;
-typedef mbf16 mbf16x8 __attribute__((ext_vector_type(8)));
-typedef mbf16 mbf16x4 __attribute__((ext_vector_type(4)));
-typedef float mfloatx4 __attribute__((ext_vector_type(4)));
-
-// activations of the MFMA kernels: v_exp_f32 + v_rcp_f32 (a few ulp; tanh to ~1e-7 absolute)
-__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
-
-__device__ __forceinline__ void split_bf16(float v, mbf16& hi, mbf16& lo) {
-    hi = (mbf16)v;
-    lo = (mbf16)(v - (float)hi);
-}
+// (the bf16 vector types, split_bf16, fsig / ftanh and ror8: seq_mfma.h, shared with gru_seq.hip)
 
 struct MFwdArgs {
     int T, B, I;
@@ -414,10 +403,6 @@ struct WFwdArgs {
 // A lane (column j) holds i, g (j < 8) or f, o (j >= 8) of unit 8w + (j & 7) for its 4 rows;
 // the partner lane j ^ 8 (DPP row_ror:8, one VALU move per value) supplies the other two
 // gates, and each lane updates 2 of the 4 (env, unit) pairs (j < 8: rows 0, 1; else 2, 3).
-__device__ __forceinline__ float ror8(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-}
-
 // Up to two independent sequences per launch (the actor's and the critic's memory: a
 // 2,048-env mini-batch is 128 workgroups, half the CUs, so one launch of both fills them):
 // blockIdx.y selects the job; a job with fewer workgroups than the grid's x leaves the rest.
@@ -1865,6 +1850,13 @@ static int step_tiles(int B) {
     // 4 tiles, G1 x 4096 6.06 -> 5.93 ms at 2 (profiles/round6/lstm_step_tiles.txt)
     return std::max(1, std::min(4, B / 2048));
 }
+
+// the same error text, launch status and tile rule for gru_seq.hip (seq_mfma.h)
+namespace pmlp_seq {
+int fail(const std::string& m) { return ::fail(m); }
+int launched(const char* what) { return ::launched(what); }
+int step_tiles(int B) { return ::step_tiles(B); }
+}  // namespace pmlp_seq
 
 PMLP_API int pmlp_lstm_fwd_mfma(int32_t T, int32_t B, int32_t H, int32_t I, const float* x, const float* wih,
                                 const float* bih, const float* bhh, const float* whh, const float* h0, const float* c0,

@@ -1,0 +1,34 @@
+// seq_mfma.h — what the matrix-core sequence kernels of lstm_seq.hip and gru_seq.hip share:
+// the bf16 vector types, the split of an fp32 value into bf16 hi + lo, the fast activations,
+// the partner-lane exchange, and the host side's error text and step-tile rule.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+typedef __bf16 mbf16;
+typedef mbf16 mbf16x8 __attribute__((ext_vector_type(8)));
+typedef mbf16 mbf16x4 __attribute__((ext_vector_type(4)));
+typedef float mfloatx4 __attribute__((ext_vector_type(4)));
+
+// activations of the MFMA kernels: v_exp_f32 + v_rcp_f32 (a few ulp; tanh to ~1e-7 absolute)
+static __device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
+static __device__ __forceinline__ float ftanh(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
+
+static __device__ __forceinline__ void split_bf16(float v, mbf16& hi, mbf16& lo) {
+    hi = (mbf16)v;
+    lo = (mbf16)(v - (float)hi);
+}
+
+// the value of lane j ^ 8 of the same row of 16 (DPP row_ror:8, one VALU move)
+static __device__ __forceinline__ float ror8(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
+}
+
+// host side, defined in lstm_seq.hip: the text behind pmlp_lstm_last_error, the status after a
+// launch, and the 16-env tiles per workgroup of a single rollout step
+namespace pmlp_seq {
+__attribute__((visibility("hidden"))) int fail(const std::string& m);
+__attribute__((visibility("hidden"))) int launched(const char* what);
+__attribute__((visibility("hidden"))) int step_tiles(int B);
+}  // namespace pmlp_seq

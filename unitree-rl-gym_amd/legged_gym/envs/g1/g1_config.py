@@ -87,6 +87,16 @@ class G1RoughCfgPPO(LeggedRobotCfgPPO):
         experiment_name = "g1"
 
 
+class G1GruCfgPPO(G1RoughCfgPPO):
+    """g1 with a GRU memory (rsl_rl's rnn_type="gru"): three quarters of the LSTM's gate columns
+    and no cell state, on the GRU sequence kernels (rsl_rl/modules/gru_seq.py)."""
+    class policy(G1RoughCfgPPO.policy):
+        rnn_type = "gru"
+
+    class runner(G1RoughCfgPPO.runner):
+        experiment_name = "g1_gru"
+
+
 class G1HeightfieldCfg(G1RoughCfg):
     """BASELINE configs[2]: G1 on the rough-terrain heightfield (utils/terrain.py's
     curriculum map: 10 x 20 tiles of slopes, stairs and obstacles).  The reference

@@ -121,9 +121,11 @@ def get_args(argv=None):
 
 
 def export_policy_as_jit(actor_critic, path):
-    """policy_1.pt (scripted MLP actor) or policy_lstm_1.pt (PolicyExporterLSTM)."""
+    """policy_1.pt (scripted MLP actor), policy_lstm_1.pt (PolicyExporterLSTM) or
+    policy_gru_1.pt (PolicyExporterGRU), by the kind of the actor's memory."""
     if hasattr(actor_critic, "memory_a"):
-        PolicyExporterLSTM(actor_critic).export(path)
+        gru = isinstance(actor_critic.memory_a.rnn, torch.nn.GRU)
+        (PolicyExporterGRU if gru else PolicyExporterLSTM)(actor_critic).export(path)
         return
     os.makedirs(path, exist_ok=True)
     model = _plain_linear(copy.deepcopy(actor_critic.actor).to("cpu"))
@@ -172,3 +174,30 @@ class PolicyExporterLSTM(torch.nn.Module):
         os.makedirs(path, exist_ok=True)
         self.to("cpu")
         torch.jit.script(self).save(os.path.join(path, "policy_lstm_1.pt"))
+
+
+class PolicyExporterGRU(torch.nn.Module):
+    """PolicyExporterLSTM for a GRU memory: one state buffer (hidden_state), forward(x),
+    reset_memory()."""
+
+    def __init__(self, actor_critic):
+        super().__init__()
+        self.actor = _plain_linear(copy.deepcopy(actor_critic.actor))
+        self.is_recurrent = actor_critic.is_recurrent
+        self.memory = copy.deepcopy(actor_critic.memory_a.rnn)
+        self.memory.cpu()
+        self.register_buffer("hidden_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
+
+    def forward(self, x):
+        out, h = self.memory(x.unsqueeze(0), self.hidden_state)
+        self.hidden_state[:] = h
+        return self.actor(out.squeeze(0))
+
+    @torch.jit.export
+    def reset_memory(self):
+        self.hidden_state[:] = 0.0
+
+    def export(self, path):
+        os.makedirs(path, exist_ok=True)
+        self.to("cpu")
+        torch.jit.script(self).save(os.path.join(path, "policy_gru_1.pt"))

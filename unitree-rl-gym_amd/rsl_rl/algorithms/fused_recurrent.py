@@ -39,9 +39,10 @@ def _pad4(n):
     return (n + 3) // 4 * 4
 
 
-def supported(ac, num_envs, num_mini_batches):
-    """The policy shapes the fused recurrent step covers (else the autograd update runs)."""
-    if not getattr(ac, "is_recurrent", False) or not hasattr(ac, "memory_a") or num_envs % num_mini_batches:
+def heads_supported(ac):
+    """The recurrent policies whose two Linear/ELU/Linear heads pmlp_heads_forward(_act) and
+    pmlp_heads_backward take, whatever the kind of the memories in front of them."""
+    if not getattr(ac, "is_recurrent", False) or not hasattr(ac, "memory_a"):
         return False
     for seq in (ac.actor, ac.critic):
         if not isinstance(seq, nn.Sequential) or len(seq) != 3 or not isinstance(seq[0], nn.Linear) or \
@@ -55,14 +56,20 @@ def supported(ac, num_envs, num_mini_batches):
         return False
     if ac.critic[2].out_features != 1:
         return False
+    return all(m.rnn.hidden_size == (ac.actor if m is ac.memory_a else ac.critic)[0].in_features
+               for m in (ac.memory_a, ac.memory_c))
+
+
+def supported(ac, num_envs, num_mini_batches):
+    """The policy shapes the fused recurrent step covers (else the autograd update runs)."""
+    if not heads_supported(ac) or num_envs % num_mini_batches:
+        return False
     for m in (ac.memory_a, ac.memory_c):
         rnn = m.rnn
         # (inputs past 64 columns: the wide matrix-core kernels, hidden 64 only)
         if not isinstance(rnn, nn.LSTM) or rnn.num_layers != 1 or not rnn.bias or rnn.batch_first or \
                 rnn.hidden_size not in (32, 64, 128) or \
                 rnn.input_size > (lstm_seq.WIDE_MAX_INPUT if rnn.hidden_size == 64 else 64):
-            return False
-        if rnn.hidden_size != (ac.actor if m is ac.memory_a else ac.critic)[0].in_features:
             return False
     return True
 

@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from rsl_rl.modules import lstm_seq
+from rsl_rl.modules import gru_seq, lstm_seq
 from rsl_rl.modules import mfma_mlp as mm
 
 
@@ -519,7 +519,7 @@ class FusedRollout:
 class RecurrentRollout:
     """PPO.act + RolloutStorage.add_transitions and PPO.process_env_step for
     ActorCriticRecurrent on the GPU: the state before the step is saved, both memories
-    step in place on the LSTM kernel, the fp32 MLP heads run as torch ops, and pmlp_act /
+    step in place on the LSTM or the GRU kernel, the fp32 MLP heads run as torch ops, and pmlp_act /
     pmlp_store_step sample the actions, compute the log-probability and write the storage
     rows and the bootstrapped reward in one launch each (the distribution object and the
     per-field copies of the generic path are never built).  Capturable: the noise is
@@ -548,7 +548,12 @@ class RecurrentRollout:
         self.heads = None
         # pmlp_act inside the heads' launch where the shapes allow (PMLP_HEADS_ACT=0: two launches)
         self.fuse_act = os.environ.get("PMLP_HEADS_ACT", "1") != "0"
-        if fused_recurrent.supported(ac, self.N, 1) and ac.memory_a.rnn.hidden_size == ac.memory_c.rnn.hidden_size:
+        # GRU memories on the sequence kernels (gru_seq.py): their step is always the update's
+        # arithmetic (one kernel), and the heads' launch takes their output as it takes an LSTM's
+        probe = ac.std.new_empty(1, 1)
+        self.gru = all(gru_seq.usable(m.rnn, probe) for m in (ac.memory_a, ac.memory_c))
+        if (fused_recurrent.supported(ac, self.N, 1) or (self.gru and fused_recurrent.heads_supported(ac))) and \
+                ac.memory_a.rnn.hidden_size == ac.memory_c.rnn.hidden_size:
             dev = ac.std.device
             self.heads = [ac.actor, ac.critic]
             self.y0 = [torch.empty(self.N, s[0].out_features, device=dev) for s in self.heads]
@@ -561,6 +566,15 @@ class RecurrentRollout:
         if hs is None or not isinstance(hs, tuple) or hs[0].shape != (1, B, H) or hs[0].device != x.device:
             with torch.inference_mode(False):
                 mem.hidden_states = (torch.zeros(1, B, H, device=x.device), torch.zeros(1, B, H, device=x.device))
+        return mem.hidden_states
+
+    def _gstate(self, mem, x):
+        """A GRU memory's static state buffer (created as Memory.step_ creates it)."""
+        B, H = x.shape[0], mem.rnn.hidden_size
+        hs = mem.hidden_states
+        if not torch.is_tensor(hs) or hs.shape != (1, B, H) or hs.device != x.device:
+            with torch.inference_mode(False):
+                mem.hidden_states = torch.zeros(1, B, H, device=x.device)
         return mem.hidden_states
 
     def _mstep_pair(self, ma, obs, sa, mc, cobs, sc):
@@ -598,6 +612,13 @@ class RecurrentRollout:
             else:
                 ha = ma.step_(obs, save=(sa[0], sa[1]))
                 hc = mc.step_(cobs, save=(sc[0], sc[1]))
+        elif self.gru:
+            # one state tensor per memory; both memories step in one launch, which also writes
+            # the state before the step into the storage slot
+            shape = (1, self.N, H)
+            sa, sc = storage.hidden_state_slots(t, [shape], [shape])
+            ha, hc = gru_seq.gru_step_pair_([(ma.rnn, obs, self._gstate(ma, obs), sa[0]),
+                                             (mc.rnn, cobs, self._gstate(mc, cobs), sc[0])])
         else:
             storage._save_hidden_states(ac.get_hidden_states())
             ha, hc = ma(obs), mc(cobs)
@@ -638,14 +659,16 @@ class RecurrentRollout:
         pass  # nothing is deferred: store() issues its launch at once
 
     def _reset_states(self):
-        """The memories' (h, c) buffers [1, N, H] that ActorCriticRecurrent.reset(dones) masks,
-        when the store launch can zero them itself (static contiguous fp32 LSTM states of one
-        width), else None."""
+        """The memories' state buffers [1, N, H] ((h, c) of an LSTM, h of a GRU) that
+        ActorCriticRecurrent.reset(dones) masks, when the store launch can zero them itself
+        (static contiguous fp32 states of one width), else None."""
         ac = self.alg.actor_critic
         out, H = [], None
         for mem in (ac.memory_a, ac.memory_c):
             hs = mem.hidden_states
-            if not isinstance(mem.rnn, torch.nn.LSTM) or not isinstance(hs, tuple):
+            if isinstance(mem.rnn, torch.nn.GRU) and torch.is_tensor(hs):
+                hs = (hs,)
+            elif not isinstance(mem.rnn, torch.nn.LSTM) or not isinstance(hs, tuple):
                 return None
             for h in hs:
                 if not (h.is_cuda and h.dtype == torch.float32 and h.is_contiguous() and h.dim() == 3 and

@@ -21,7 +21,7 @@ import torch.optim as optim
 
 from rsl_rl.algorithms import fused_recurrent, fused_step
 from rsl_rl.modules import ActorCritic
-from rsl_rl.modules import mfma_mlp
+from rsl_rl.modules import gru_seq, mfma_mlp
 from rsl_rl.storage import RolloutStorage
 from rsl_rl.storage.rollout_storage import minibatch_permutation
 from rsl_rl.utils import capture_without_gc
@@ -74,13 +74,17 @@ class PPO:
         # (library bf16 GEMMs under autocast drift inside a captured graph on this ROCm;
         #  the MFMA MLP kernels are deterministic and capture cleanly)
         # recurrent policies train in the dense form (storage.recurrent_dense_mini_batch_generator,
-        # modules/lstm_seq.py): fixed shapes and no host sync, so their update captures too.
-        # The dense form covers one-layer LSTMs; a GRU (or a deeper LSTM) keeps rsl_rl's
-        # padded-trajectory generator and the eager update.
+        # modules/lstm_seq.py, modules/gru_seq.py): fixed shapes and no host sync, so their
+        # update captures too.  The dense form covers one-layer LSTMs anywhere, and on a GPU the
+        # GRUs the sequence kernels take (gru_seq.usable: one layer, hidden 64, inputs <= 64);
+        # any other GRU, a GRU on the CPU and a deeper LSTM keep rsl_rl's padded-trajectory
+        # generator and the eager update.
+        rnns = [getattr(getattr(self.actor_critic, m, None), "rnn", None) for m in ("memory_a", "memory_c")]
+        probe = torch.empty(1, 1, device=self.device)
         self._dense_recurrent = getattr(self.actor_critic, "is_recurrent", False) and \
             hasattr(self.actor_critic, "act_dense") and \
-            all(isinstance(getattr(getattr(self.actor_critic, m, None), "rnn", None), nn.LSTM) and
-                getattr(self.actor_critic, m).rnn.num_layers == 1 for m in ("memory_a", "memory_c"))
+            (all(isinstance(r, nn.LSTM) and r.num_layers == 1 for r in rnns) or
+             all(gru_seq.usable(r, probe) for r in rnns))
         self.use_graph = on_gpu and (not getattr(self.actor_critic, "is_recurrent", False) or
                                      self._dense_recurrent) and \
             self.optimizer.defaults.get("capturable", False) and \

@@ -1,7 +1,7 @@
 import torch
 import torch.nn as nn
 
-from rsl_rl.modules import lstm_seq
+from rsl_rl.modules import gru_seq, lstm_seq
 from rsl_rl.modules.actor_critic import ActorCritic, get_activation  # noqa: F401
 from rsl_rl.utils import unpad_trajectories
 
@@ -47,12 +47,14 @@ class ActorCriticRecurrent(ActorCritic):
         return self.memory_a.hidden_states, self.memory_c.hidden_states
 
     def rollout_capturable(self):
-        """Both memories step on the LSTM kernels in place (a graph-capturable rollout)."""
+        """Both memories step on the LSTM kernels, or both on the GRU kernels, in place (a
+        graph-capturable rollout)."""
         p = self.memory_a.rnn.weight_hh_l0
         probe = p.new_empty(1, 1)
-        return all(lstm_seq.usable(m.rnn, probe) for m in (self.memory_a, self.memory_c))
+        return any(all(seq.usable(m.rnn, probe) for m in (self.memory_a, self.memory_c))
+                   for seq in (lstm_seq, gru_seq))
 
-    # ---- dense update form (no padded trajectories; rsl_rl/modules/lstm_seq.py) ----
+    # ---- dense update form (no padded trajectories; rsl_rl/modules/lstm_seq.py, gru_seq.py) ----
     def act_dense(self, observations, hidden_states, reset):
         """update_distribution over a [T,B,O] sequence: the memory runs all T steps with
         resets before step t where reset[t]; the distribution covers the T*B rows."""
@@ -74,9 +76,11 @@ class ActorCriticRecurrent(ActorCritic):
 
 class Memory(torch.nn.Module):
     """rsl_rl v1.0.2 Memory.  On a GPU the one-layer LSTM runs on the sequence kernels of
-    lstm_seq.py: in rollout mode one step updates the state buffers IN PLACE (static
-    addresses: the collection loop can be captured in a HIP graph), and reset(dones)
-    zeroes rows with a mask (no device->host sync)."""
+    lstm_seq.py, and the one-layer GRU (hidden 64, inputs <= 64) on those of gru_seq.py: in
+    rollout mode one step updates the state buffers IN PLACE (static addresses: the
+    collection loop can be captured in a HIP graph), and reset(dones) zeroes rows with a mask
+    (no device->host sync).  hidden_states is what the torch module keeps: an (h, c) tuple of
+    [1, B, H] tensors for an LSTM, a single [1, B, H] tensor for a GRU."""
 
     def __init__(self, input_size, type="lstm", num_layers=1, hidden_size=256):
         super().__init__()
@@ -90,17 +94,24 @@ class Memory(torch.nn.Module):
                 raise ValueError("Hidden states not passed to memory module during policy update")
             out, _ = self.rnn(input, hidden_states)
             out = unpad_trajectories(out, masks)
-        elif lstm_seq.usable(self.rnn, input):  # rollout mode on the kernel: state updated in place
+        elif lstm_seq.usable(self.rnn, input) or gru_seq.usable(self.rnn, input):
+            # rollout mode on the kernel: state updated in place
             out = self.step_(input)
         else:  # rollout mode: one step, keep the state
             out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
         return out
 
     def step_(self, input, save=None):
-        """Rollout step on the LSTM kernel, the state buffers updated in place (created as
-        zeros on first use); save = (h_dst, c_dst) receives the state the step starts from."""
+        """Rollout step on the LSTM / GRU kernel, the state buffers updated in place (created
+        as zeros on first use); save = (h_dst, c_dst), for a GRU h_dst alone, receives the state
+        the step starts from."""
         B, H = input.shape[0], self.rnn.hidden_size
         hs = self.hidden_states
+        if isinstance(self.rnn, nn.GRU):
+            if not torch.is_tensor(hs) or hs.shape != (1, B, H) or hs.device != input.device:
+                with torch.inference_mode(False):
+                    self.hidden_states = torch.zeros(1, B, H, device=input.device)
+            return gru_seq.gru_step_pair_([(self.rnn, input, self.hidden_states, save)])[0]
         if hs is None or not isinstance(hs, tuple) or hs[0].shape != (1, B, H) or hs[0].device != input.device:
             with torch.inference_mode(False):
                 self.hidden_states = (torch.zeros(1, B, H, device=input.device),
@@ -110,8 +121,12 @@ class Memory(torch.nn.Module):
     def dense(self, input, hidden_states, reset):
         """[T,B,I] -> [T,B,H]: all T steps from hidden_states (the state saved at t = 0),
         zeroing the state before step t where reset[t] (dense form of the padded update)."""
-        if not isinstance(self.rnn, nn.LSTM):
-            raise NotImplementedError("dense memory update: LSTM only")
+        if isinstance(self.rnn, nn.GRU):
+            if gru_seq.usable(self.rnn, input):
+                return gru_seq.gru_dense(self.rnn, input, hidden_states, reset)
+            if self.rnn.num_layers != 1:
+                raise NotImplementedError("dense memory update: one layer")
+            return gru_seq.gru_dense_reference(self.rnn, input, hidden_states, reset)
         h0, c0 = (None, None) if hidden_states is None else hidden_states
         if lstm_seq.usable(self.rnn, input):
             return lstm_seq.lstm_dense(self.rnn, input, h0, c0, reset)
