@@ -498,41 +498,32 @@ PMLP_API int pmlp_lstm_step(int32_t B, int32_t H, const float* gx, const float* 
                             float* h_save, float* c_save, void* stream);
 PMLP_API int pmlp_lstm_bwd(int32_t T, int32_t B, int32_t H, const float* whh, const float* c0, const uint8_t* reset,
                            const float* c_out, const float* gact, const float* dh_out, float* dgx, void* stream);
-/* The update's dense sequences on the matrix cores (hidden 64, input <= 64): the forward of
- * pmlp_lstm_fwd_x and the backward of pmlp_lstm_bwd with the per-step products
- * [x_t | h_{t-1}] . [W_ih | W_hh]^T and dG . W_hh as bf16 MFMAs (fp32 accumulation, the cell
- * state and every output fp32).  Same outputs and layouts as the fp32 kernels, to bf16 operand
- * rounding; the rollout's step (pmlp_lstm_step) stays fp32. */
-PMLP_API int pmlp_lstm_fwd_mfma(int32_t T, int32_t B, int32_t H, int32_t I, const float* x, const float* wih,
-                                const float* bih, const float* bhh, const float* whh, const float* h0, const float* c0,
-                                const uint8_t* reset, float* h_out, float* c_out, float* gact, float* xh, void* stream);
-PMLP_API int pmlp_lstm_bwd_mfma(int32_t T, int32_t B, int32_t H, const float* whh, const float* c0,
-                                const uint8_t* reset, const float* c_out, const float* gact, const float* dh_out,
-                                float* dgx, void* stream);
-/* pmlp_lstm_bwd_mfma plus the three weight gradients (the fused recurrent step): per
- * workgroup of 16 envs (pmlp_lstm_bwd_dw_blocks(B) of them) the partial sums over its envs
- * and the T steps of dG^T [x | h_prev | 1] (xh: the rows pmlp_lstm_fwd_mfma wrote), as one
- * slab row [dW_ih (4H x I) | dW_hh (4H x H) | db (4H)] of 4H (I + H + 1) floats in torch's
- * row order (summed over the rows by pmlp_reduce_slabs; db is the gradient of b_ih and b_hh).
- * The gate gradients themselves are not written.  H = 64, I + H + 1 <= 128.            */
-/* One rollout step of a hidden-64 memory on the matrix cores: the arithmetic of
- * pmlp_lstm_fwd_mfma at T = 1 (so the rollout's log-probabilities come from the same
- * numbers the update recomputes), input projection inside, h / c [B, 64] updated in place;
- * h_save / c_save (both or neither) receive the state the step starts from.   I <= 64.  */
-PMLP_API int pmlp_lstm_step_mfma(int32_t B, int32_t H, int32_t I, const float* x, const float* wih, const float* bih,
-                                 const float* bhh, const float* whh, float* h, float* c, float* h_save, float* c_save,
-                                 void* stream);
-PMLP_API int32_t pmlp_lstm_bwd_dw_blocks(int32_t B);
-PMLP_API int pmlp_lstm_bwd_dw_mfma(int32_t T, int32_t B, int32_t H, int32_t I, const float* whh, const float* c0,
-                                   const uint8_t* reset, const float* c_out, const float* gact, const float* dh_out,
-                                   const float* xh, float* slab, void* stream);
-/* The actor's and the critic's memory in ONE launch each way (rsl_rl ActorCriticRecurrent's
- * memory_a / memory_c: independent sequences over the same [T, B] mini-batch and reset mask;
- * one 2,048-env mini-batch is 128 workgroups, half of the 256 CUs).  Per job exactly
- * pmlp_lstm_fwd_mfma (x, w_ih, b_ih, b_hh, w_hh, h0, c0 -> h_out, c_out, gact, xh) and
- * pmlp_lstm_bwd_dw_mfma (w_hh, c0, c_out, gact, dh_out, xh -> slab).  1 <= njobs <= 2. */
+/* ---- the LSTM on the matrix cores: hidden 64, fp32 tensors, 1..2 memories (jobs) per launch
+ * side by side in the grid (rsl_rl ActorCriticRecurrent's memory_a / memory_c: independent
+ * sequences over the same [T, B] mini-batch and reset mask; one 2,048-env mini-batch is 128
+ * workgroups, half of the 256 CUs).  Outputs and layouts are those of the fp32 kernels above.
+ *   arithmetic: per step the gate pre-activations are [x_t | h_{t-1}] . [W_ih | W_hh]^T, and the
+ *             backward's dh_{t-1} = dG . W_hh, as bf16 MFMAs with every operand split into bf16
+ *             hi + lo (hi.hi + hi.lo + lo.hi, near fp32), fp32 accumulation from the fp32 bias
+ *             b_ih + b_hh; the cell state and every output are fp32.
+ *   forward:  x, w_ih, b_ih, b_hh, w_hh, h0, c0 (NULL: zeros) -> h_out, c_out [T,B,64],
+ *             gact [T,B,256], xh [T,B,I+65] = [x | h_prev | 1] (h_prev: the state the step starts
+ *             from, after a reset), all four required.  1 <= I <= 64.
+ *   backward: w_hh, c0, c_out, gact, xh, dh_out -> slab: per workgroup of 16 envs
+ *             (pmlp_lstm_bwd_dw_blocks(B) of them) the partial sums over its envs and the T
+ *             steps of dG^T [x | h_prev | 1], one slab row [dW_ih (256 x I) | dW_hh (256 x 64) |
+ *             db (256)] of 256 (I + 65) floats in torch's row order (summed over the rows by
+ *             pmlp_reduce_slabs; db is the gradient of b_ih and of b_hh).  The gate gradients
+ *             themselves are not written.  I + 65 <= 128, i.e. 1 <= I <= 63.
+ *   step:     one rollout step, the forward at T = 1 (so the rollout's log-probabilities come
+ *             from the same numbers the update recomputes) with h = h_out, c = c_out [B,64] read
+ *             and overwritten in place; x, w_ih, b_ih, b_hh, w_hh as in the forward, the other
+ *             fields are ignored.  1 <= I <= 64.
+ *   h_save / c_save (step only, optional, both or neither) receive the state the step starts
+ *             from (the rollout storage's saved hidden state).
+ * Every check runs before the launch (text in pmlp_lstm_last_error).                         */
 typedef struct pmlp_lstm_job {
-    int32_t I;                                   /* input width, 1..63                   */
+    int32_t I;                                   /* input width (see above)               */
     const float *x, *w_ih, *b_ih, *b_hh, *w_hh;  /* [T,B,I], torch nn.LSTM parameters   */
     const float *h0, *c0;                        /* [B,64] state the sequence starts from */
     float *h_out, *c_out, *gact, *xh;            /* forward outputs (backward inputs)     */
@@ -542,18 +533,22 @@ typedef struct pmlp_lstm_job {
 } pmlp_lstm_job;
 PMLP_API int pmlp_lstm_fwd_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t T, int32_t B, int32_t H,
                                      const uint8_t* reset, void* stream);
+PMLP_API int32_t pmlp_lstm_bwd_dw_blocks(int32_t B);
 PMLP_API int pmlp_lstm_bwd_dw_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t T, int32_t B, int32_t H,
                                         const uint8_t* reset, void* stream);
-/* The rollout's memory step of both memories in one launch: per job pmlp_lstm_step_mfma with
- * h = h_out, c = c_out (the state [B,64], updated in place), h_save / c_save optional (both
- * or neither); x, w_ih, b_ih, b_hh, w_hh as above; the other fields are ignored.          */
 PMLP_API int pmlp_lstm_step_mfma_jobs(int32_t njobs, const pmlp_lstm_job* jobs, int32_t B, int32_t H, void* stream);
+/* The autograd path's backward of one memory: the backward above with the gate gradients
+ * dgx [T,B,256] as its only output (pmlp_lstm_bwd's arguments; the caller forms the weight
+ * gradients).                                                                                */
+PMLP_API int pmlp_lstm_bwd_mfma(int32_t T, int32_t B, int32_t H, const float* whh, const float* c0,
+                                const uint8_t* reset, const float* c_out, const float* gact, const float* dh_out,
+                                float* dgx, void* stream);
 
 /* ---- wide inputs: a hidden-64 memory whose input is 65 .. pmlp_lstm_wide_max_input() (384)
  * columns, e.g. an observation row with the height scan.  W_ih no longer fits the sequence
  * kernel's lanes, so the input projection runs first as one split-bf16 matrix-core product
  * over all T*B rows, gx = x W_ih^T + b_ih + b_hh, and the sequence kernel starts each step's
- * accumulators from the env's gx row (the arithmetic of pmlp_lstm_fwd_mfma otherwise).
+ * accumulators from the env's gx row (the arithmetic of pmlp_lstm_job otherwise).
  *   forward:  x [T,B,I] (rows of I floats: 4-byte alignment is all they have), w_ih, b_ih,
  *             b_hh, w_hh, h0, c0 (NULL: zeros) -> gx [T,B,256], h_out, c_out [T,B,64],
  *             gact [T,B,256], hp [T,B,65] = [h_prev | 1] (the backward's operand)
@@ -586,7 +581,7 @@ PMLP_API int pmlp_lstm_step_wide_jobs(int32_t njobs, const pmlp_lstm_wide_job* j
 
 /* ---- recurrent memory: GRU.  rsl_rl v1.0.2 Memory with rnn_type="gru" (one-layer nn.GRU,
  * gate order r, z, n) in the dense form of the LSTM above, on the matrix cores with the
- * arithmetic of pmlp_lstm_fwd_mfma (split-bf16 products, fp32 accumulation from the fp32
+ * arithmetic of pmlp_lstm_job (split-bf16 products, fp32 accumulation from the fp32
  * bias, fp32 state).  Hidden 64, inputs 1..64 (pmlp_gru_supported), fp32 tensors.
  *   gi = x_t W_ih^T + b_ih, gh = h W_hh^T + b_hh, r = sig(gi_r + gh_r), z = sig(gi_z + gh_z),
  *   n = tanh(gi_n + r gh_n), h = (1 - z) n + z h;  h is zeroed before step t where reset[t].

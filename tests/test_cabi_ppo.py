@@ -34,6 +34,16 @@ def test_library_exports_every_declared_symbol(lib):
     assert not missing, missing
 
 
+def test_matrix_core_lstm_has_one_entry_per_kernel(lib):
+    """The single-memory forms of the jobs entries are gone from the header and from the library
+    (a jobs entry takes njobs = 1); pmlp_lstm_bwd_mfma, the autograd path's backward, stays."""
+    names = declared_functions()
+    for gone in ("pmlp_lstm_fwd_mfma", "pmlp_lstm_bwd_dw_mfma", "pmlp_lstm_step_mfma"):
+        assert gone not in names and not hasattr(lib, gone), gone
+        assert gone + "_jobs" in names and hasattr(lib, gone + "_jobs")
+    assert "pmlp_lstm_bwd_mfma" in names
+
+
 def test_ctypes_job_structs_match_c_layout(tmp_path):
     from rsl_rl.modules import mfma_mlp as mm
     src = tmp_path / "sz.c"
@@ -112,6 +122,15 @@ def test_recurrent_and_bookkeeping_entries_refuse_bad_arguments(lib):
     jobs[0].I = 44
     assert L.pmlp_lstm_bwd_dw_mfma_jobs(1, jobs, 24, 64, 64, None, None) != 0  # null buffers
     assert b"pmlp_lstm_bwd_dw_mfma_jobs" in L.pmlp_lstm_last_error()
+    # (fake non-null aligned pointers: the status and the message arrive before any launch)
+    full = lstm_seq.LstmJob(64, *([16] * 15))
+    assert L.pmlp_lstm_bwd_dw_mfma_jobs(1, C.byref(full), 24, 64, 64, None, None) != 0  # [x | h | 1] past 128 columns
+    err = L.pmlp_lstm_last_error()
+    assert b"pmlp_lstm_bwd_dw_mfma_jobs" in err and b"input 1..63" in err
+    full.I, full.c_save = 44, None
+    assert L.pmlp_lstm_step_mfma_jobs(1, C.byref(full), 64, 64, None) != 0  # h_save without c_save
+    err = L.pmlp_lstm_last_error()
+    assert b"pmlp_lstm_step_mfma_jobs" in err and b"h_save and c_save together" in err
     job = (mm.ReduceJob * 1)(mm.ReduceJob(16, 16, None, 64, 64, 2, 0, 0))
     rs = mm.ReduceStep()
     assert lib.pmlp_reduce_slabs_step(1, job, C.byref(rs), None) != 0  # no loss partials

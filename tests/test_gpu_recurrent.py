@@ -47,8 +47,9 @@ def test_lstm_kernels_match_torch(H, I):
 
 @pytest.mark.parametrize("I", [41, 47, 64, 17])
 def test_lstm_mfma_kernels_match_torch_to_bf16(I):
-    """The update's matrix-core LSTM (pmlp_lstm_fwd_mfma / _bwd_mfma: split-bf16 operands,
-    hi.hi + hi.lo + lo.hi products, fp32 accumulation and state) vs the same recurrence in
+    """The update's matrix-core LSTM (pmlp_lstm_fwd_mfma_jobs with one job / pmlp_lstm_bwd_mfma:
+    split-bf16 operands, hi.hi + hi.lo + lo.hi products, fp32 accumulation and state; I = 64 fills
+    every x slot of the forward) vs the same recurrence in
     torch fp32 ops over 24 steps with resets inside and a carried initial state: h within
     1e-4 absolute (h in [-1, 1]), the weight gradients within 1e-3 relative (norm); the
     weight-gradient operand [x | h_prev | 1] is the fp32 state."""
@@ -408,7 +409,7 @@ def test_fused_recurrent_heads_match_torch(H, M):
 
 @pytest.mark.parametrize("I", [41, 47, 17, 63])
 def test_lstm_bwd_accumulates_the_weight_gradients(I):
-    """pmlp_lstm_bwd_dw_mfma (the fused recurrent step's memory backward): the per-workgroup
+    """pmlp_lstm_bwd_dw_mfma_jobs (the fused recurrent step's memory backward): the per-workgroup
     partials of dG^T [x | h_prev | 1], summed over the slab rows, are the weight gradients of
     torch autograd through the same recurrence (resets inside, a carried initial state; env
     count not a multiple of the 16-env workgroups), within 1e-4 relative (norm)."""
@@ -425,12 +426,12 @@ def test_lstm_bwd_accumulates_the_weight_gradients(I):
     h_out, c_out = torch.empty(T, B, H, device="cuda"), torch.empty(T, B, H, device="cuda")
     gact, xh = torch.empty(T, B, 4 * H, device="cuda"), torch.empty(T, B, I + H + 1, device="cuda")
     w = [t.detach().contiguous() for t in (rnn.weight_ih_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, rnn.weight_hh_l0)]
-    lstm_seq._ok(L.pmlp_lstm_fwd_mfma(T, B, H, I, P(x), P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(h0), P(c0), P(reset),
-                                      P(h_out), P(c_out), P(gact), P(xh), st), "fwd")
     nblk = L.pmlp_lstm_bwd_dw_blocks(B)
     slab = torch.empty(nblk, 4 * H * (I + H + 1), device="cuda")
-    lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma(T, B, H, I, P(w[3]), P(c0), P(reset), P(c_out), P(gact), P(g), P(xh),
-                                         P(slab), st), "bwd_dw")
+    job = lstm_seq.LstmJob(I, P(x), P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(h0), P(c0), P(h_out), P(c_out), P(gact),
+                           P(xh), P(g), P(slab))
+    lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(1, job, T, B, H, P(reset), st), "fwd")
+    lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma_jobs(1, job, T, B, H, P(reset), st), "bwd_dw")
     tot = slab.sum(0)
     got = [tot[:4 * H * I].view(4 * H, I), tot[4 * H * I:4 * H * (I + H)].view(4 * H, H), tot[4 * H * (I + H):]]
     y_ref = lstm_seq.lstm_dense_reference(rnn, x, h0, c0, reset)
@@ -460,8 +461,8 @@ def test_recurrent_rollout_heads_kernel_matches_torch_heads():
 
 
 def test_lstm_rollout_step_mfma_in_place_matches_nn_lstm():
-    """pmlp_lstm_step_mfma (the recurrent rollout's memory step: the update's matrix-core
-    arithmetic at T = 1): h, c updated in place and the pre-step state saved, vs one nn.LSTM
+    """pmlp_lstm_step_mfma_jobs with one job (the recurrent rollout's memory step: the update's
+    matrix-core arithmetic at T = 1): h, c updated in place and the pre-step state saved, vs one nn.LSTM
     step within the split-bf16 tolerance (2e-5), over three steps."""
     torch.manual_seed(5)
     B, I, H = 1000, 44, 64
@@ -474,7 +475,7 @@ def test_lstm_rollout_step_mfma_in_place_matches_nn_lstm():
         h_ref, c_ref = h.clone(), c.clone()
         with torch.no_grad():
             y, (h_new, c_new) = rnn(x.unsqueeze(0), (h_ref, c_ref))
-        out = lstm_seq.lstm_step_mfma_(rnn, x, h, c, save=(hs, cs))
+        out, = lstm_seq.lstm_step_mfma_pair_([(rnn, x, h, c, (hs, cs))])
         assert out.data_ptr() == h.data_ptr()
         assert torch.equal(hs, h_ref) and torch.equal(cs, c_ref)
         torch.testing.assert_close(h, h_new, rtol=2e-5, atol=2e-5)
@@ -511,6 +512,69 @@ def test_lstm_step_mfma_tile_loop_is_bitwise_the_one_tile_forward(B):
     assert torch.equal(hs, h_in) and torch.equal(cs, c_in)
     assert bool(torch.isfinite(h_out).all()) and bool((h != h_in).any())
     assert torch.equal(h, h_out[0]) and torch.equal(c, c_out[0])
+
+
+def test_lstm_jobs_launch_of_two_is_bitwise_two_launches_of_one():
+    """A job's results do not depend on its neighbour in the grid: forward then bwd_dw of two
+    memories (I = 41, 47) as one launch of two jobs and as two launches of one job each leave
+    the same bits in h_out, c_out, gact, xh and the slabs, and so does one in-place step in h, c,
+    h_save and c_save.  T = 3, B = 37: three workgroups, the last with 5 live envs; resets at
+    t = 0 and inside, a carried h0 / c0; every output starts as NaN, so each is also written in
+    full.  (FusedRecurrentStep and lstm_dense launch one job where a memory stands alone.)"""
+    from rsl_rl.modules import mfma_mlp as mm
+    torch.manual_seed(41)
+    T, B, H, Is = 3, 37, 64, (41, 47)
+    L, P, st = lstm_seq._lib(), mm._p, mm._stream()
+    rnns = [torch.nn.LSTM(I, H).cuda() for I in Is]
+    ws = [[t.detach().contiguous() for t in (r.weight_ih_l0, r.bias_ih_l0, r.bias_hh_l0, r.weight_hh_l0)] for r in rnns]
+    xs = [torch.randn(T, B, I, device="cuda") for I in Is]
+    h0 = [0.5 * torch.randn(B, H, device="cuda") for _ in Is]
+    c0 = [0.5 * torch.randn(B, H, device="cuda") for _ in Is]
+    dh = [torch.randn(T, B, H, device="cuda") for _ in Is]
+    reset = (torch.rand(T, B, device="cuda") < 0.3).to(torch.uint8)
+    reset[0, :5] = 1
+    reset[0, 5:] = 0
+    assert bool(reset[1:].any())
+    nblk = L.pmlp_lstm_bwd_dw_blocks(B)
+    assert nblk == 3
+    f = lambda *s: torch.full(s, float("nan"), device="cuda")  # noqa: E731
+
+    def dense(groups):  # groups: the memories of each launch
+        out = [dict(h_out=f(T, B, H), c_out=f(T, B, H), gact=f(T, B, 4 * H), xh=f(T, B, I + H + 1),
+                    slab=f(nblk, 4 * H * (I + H + 1))) for I in Is]
+        launches = []
+        for g in groups:
+            jobs = (lstm_seq.LstmJob * len(g))()
+            for k, n in enumerate(g):
+                o, w = out[n], ws[n]
+                jobs[k] = lstm_seq.LstmJob(Is[n], P(xs[n]), P(w[0]), P(w[1]), P(w[2]), P(w[3]), P(h0[n]), P(c0[n]),
+                                           P(o["h_out"]), P(o["c_out"]), P(o["gact"]), P(o["xh"]), P(dh[n]), P(o["slab"]))
+            lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(len(g), jobs, T, B, H, P(reset), st), "fwd_mfma_jobs")
+            launches.append(jobs)
+        for g, jobs in zip(groups, launches):
+            lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma_jobs(len(g), jobs, T, B, H, P(reset), st), "bwd_dw_mfma_jobs")
+        torch.cuda.synchronize()
+        return out
+
+    def step(groups):
+        out = [dict(h=h0[n].clone(), c=c0[n].clone(), h_save=f(B, H), c_save=f(B, H)) for n in range(2)]
+        for g in groups:
+            jobs = (lstm_seq.LstmJob * len(g))()
+            for k, n in enumerate(g):
+                o, w = out[n], ws[n]
+                jobs[k] = lstm_seq.LstmJob(Is[n], P(xs[n][0]), P(w[0]), P(w[1]), P(w[2]), P(w[3]), None, None,
+                                           P(o["h"]), P(o["c"]), None, None, None, None, P(o["h_save"]), P(o["c_save"]))
+            lstm_seq._ok(L.pmlp_lstm_step_mfma_jobs(len(g), jobs, B, H, st), "step_mfma_jobs")
+        torch.cuda.synchronize()
+        return out
+
+    for run in (dense, step):
+        two, ones = run([(0, 1)]), run([(0,), (1,)])
+        for n in range(2):
+            for name in two[n]:
+                assert torch.equal(two[n][name], ones[n][name]), (run.__name__, n, name)
+    for n, o in enumerate(two):  # (the step's: it moved the state, and saved the one it started from)
+        assert torch.equal(o["h_save"], h0[n]) and torch.equal(o["c_save"], c0[n]) and bool((o["h"] != h0[n]).any())
 
 
 @pytest.mark.parametrize("done_dtype", [torch.bool, torch.int64])
@@ -618,7 +682,7 @@ def test_recurrent_heads_matrix_core_form_is_bitwise_the_valu_form():
     """The heads' products on the matrix cores (default) against the VALU form
     (PMLP_HEADS_MFMA=0, read once per process: two probe processes), y0, out, dh and the
     weight-gradient slabs digested, on 20,003 rows (the forward's matrix-core form, ragged
-    last tiles).  Each f32 MFMA chain keeps the VALU form's fma order (lstm_seq.hip)."""
+    last tiles).  Each f32 MFMA chain keeps the VALU form's fma order (heads.hip)."""
     import os
     import subprocess
     import sys

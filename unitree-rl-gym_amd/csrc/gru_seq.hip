@@ -28,10 +28,9 @@
 
 namespace {
 
-constexpr int ME = 16, MH = 64, MG = 256, MKX = 64;  // envs per workgroup, hidden, saved row, x slots
-constexpr int MLDA = MKX + MH + 8;                   // LDS row stride of [x | h] (bf16): 272 B
-constexpr int GK = 3 * MH;                           // K of the backward's product: [da_r | da_z | da_hn]
-constexpr int GLD = GK + 8;                          // LDS row stride of it (bf16): 400 B
+// (ME, MH, MG, MKX, MLDA: seq_mfma.h, shared with lstm_seq.hip)
+constexpr int GK = 3 * MH;   // K of the backward's product: [da_r | da_z | da_hn]
+constexpr int GLD = GK + 8;  // LDS row stride of it (bf16): 400 B
 
 struct GFwdArgs {
     int T, B, I;

@@ -1,5 +1,5 @@
 // The rollout's policy noise and Gaussian log-density, shared by pmlp_act (ppo_mlp.hip), the
-// fused rollout forward and the recurrent heads' fused sampling (lstm_seq.hip), so all of them
+// fused rollout forward and the recurrent heads' fused sampling (heads.hip), so all of them
 // compute the same bits: Philox4x32-10 keyed by the rollout seed, counter (draw, env row,
 // action quad, 0x5050), Box-Muller pairs (rsl_rl ActorCritic.act: Normal(mu, std).sample()).
 #pragma once

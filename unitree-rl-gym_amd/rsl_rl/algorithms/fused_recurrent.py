@@ -6,7 +6,7 @@ mini-batches; the dense form is storage.recurrent_dense_mini_bat
 What the autograd update ran per mini-batch: the two LSTM kernels, ~10 library GEMMs for the
 heads' forward and backward, ELU / ELU' / bias-sum / copy launches, the loss kernels, the
 LSTM weight-gradient product, clip_grad_norm_'s per-tensor norms and torch's Adam.  Here
-(csrc/lstm_seq.hip, csrc/ppo_mlp.hip through include/ppo_mlp.h):
+(csrc/lstm_seq.hip, csrc/heads.hip, csrc/ppo_mlp.hip through include/ppo_mlp.h):
     1   LSTM forward, actor and critic memories side by side (matrix-core kernels, fp32
         state, pmlp_lstm_fwd_mfma_jobs: one 2,048-env memory alone fills half the CUs)
     1   both heads forward, fp32 (pmlp_heads_forward)
@@ -90,7 +90,7 @@ class FusedRecurrentStep:
         # flat parameter layout: each head's [W0 | b0 | W1 | b1] contiguous (the slab order of
         # pmlp_heads_backward), every block / LSTM tensor starting on 16 bytes
         # and each memory's [w_ih | w_hh | b_ih | b_hh] contiguous (the slab order of
-        # pmlp_lstm_bwd_dw_mfma, b_ih first)
+        # pmlp_lstm_bwd_dw_mfma_jobs, b_ih first)
         groups = [[s[0].weight, s[0].bias, s[2].weight, s[2].bias] for s in self.heads] + [[ac.std]] + \
             [[r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0] for r in self.rnns]
         params = [p for g in groups for p in g]
@@ -229,8 +229,11 @@ class FusedRecurrentStep:
         reset = reset.contiguous()
         # 1. the memories over the T steps (zeroing the state where reset[t])
         xs, hids = (obs, cobs), (hid_a, hid_c)
-        wid = [n for n in range(2) if self.wide[n]]  # on the wide kernels, side by side in one launch
-        both = self.mfma[0] and self.mfma[1] and not wid  # both memories in one narrow launch each way
+        # each set side by side in one launch each way: the wide kernels, the narrow matrix-core
+        # kernels; an fp32 memory (hidden 32 / 128, or 64 inputs at hidden 64) runs alone
+        wid = [n for n in range(2) if self.wide[n]]
+        narrow = [n for n in range(2) if self.mfma[n] and not self.wide[n]]
+        fp32 = [n for n in range(2) if not self.mfma[n]]
         if wid:
             wjobs = (lstm_seq.LstmWideJob * len(wid))()
             for k, n in enumerate(wid):
@@ -240,24 +243,22 @@ class FusedRecurrentStep:
                                                 P(self.c_out[n]), P(self.gact[n]), P(self.gx[n]), P(self.hp[n]),
                                                 P(self.dh[n]), P(self.dgx[n]), P(self.lslab[n]), P(self.lslab_ih[n]))
             lstm_seq._ok(L.pmlp_lstm_fwd_wide_jobs(len(wid), wjobs, T, mb, H, P(reset), st), "pmlp_lstm_fwd_wide_jobs")
-        if both:
-            jobs = (lstm_seq.LstmJob * 2)()
-            for n in range(2):
+        if narrow:
+            jobs = (lstm_seq.LstmJob * len(narrow))()
+            for k, n in enumerate(narrow):
                 r, (h0, c0) = self.rnns[n], (t.reshape(mb, H) for t in hids[n])
-                jobs[n] = lstm_seq.LstmJob(self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0), P(r.bias_hh_l0),
+                jobs[k] = lstm_seq.LstmJob(self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0), P(r.bias_hh_l0),
                                            P(r.weight_hh_l0), P(h0), P(c0), P(self.h_out[n]), P(self.c_out[n]),
                                            P(self.gact[n]), P(self.xh[n]), P(self.dh[n]), P(self.lslab[n]))
-            lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(2, jobs, T, mb, H, P(reset), st), "pmlp_lstm_fwd_mfma_jobs")
-        single = [] if both else [n for n in range(2) if not self.wide[n]]  # one launch per memory
-        for n in single:
+            lstm_seq._ok(L.pmlp_lstm_fwd_mfma_jobs(len(narrow), jobs, T, mb, H, P(reset), st),
+                         "pmlp_lstm_fwd_mfma_jobs")
+        for n in fp32:
             r = self.rnns[n]
             h0, c0 = (t.reshape(mb, H) for t in hids[n])
-            args = (T, mb, H, self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0), P(r.bias_hh_l0),
-                    P(r.weight_hh_l0), P(h0), P(c0), P(reset), P(self.h_out[n]), P(self.c_out[n]), P(self.gact[n]))
-            if self.mfma[n]:
-                lstm_seq._ok(L.pmlp_lstm_fwd_mfma(*args, P(self.xh[n]), st), "pmlp_lstm_fwd_mfma")
-            else:
-                lstm_seq._ok(L.pmlp_lstm_fwd_x(*args, None, None, P(self.xh[n]), st), "pmlp_lstm_fwd_x")
+            lstm_seq._ok(L.pmlp_lstm_fwd_x(T, mb, H, self.I[n], P(xs[n]), P(r.weight_ih_l0), P(r.bias_ih_l0),
+                                           P(r.bias_hh_l0), P(r.weight_hh_l0), P(h0), P(c0), P(reset),
+                                           P(self.h_out[n]), P(self.c_out[n]), P(self.gact[n]), None, None,
+                                           P(self.xh[n]), st), "pmlp_lstm_fwd_x")
         # 2. both heads: y0 and (mu, value)
         mm._ok(lib.pmlp_heads_forward(2, self._head_jobs, M, H, st), "pmlp_heads_forward")
         # 3. the loss; fp32 gradients of mu and value, the std gradient, the statistics tail
@@ -271,18 +272,14 @@ class FusedRecurrentStep:
         # 4. both heads backward: the memories' output gradients + weight-gradient partials
         mm._ok(lib.pmlp_heads_backward(2, self._head_jobs, M, H, st), "pmlp_heads_backward")
         # 5. the memories backward, with their weight gradients (slab partials) on the matrix cores
-        if both:
-            lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma_jobs(2, jobs, T, mb, H, P(reset), st), "pmlp_lstm_bwd_dw_mfma_jobs")
         if wid:  # dgx, the [dW_hh | db] slabs and the dW_ih row-chunk partials
             lstm_seq._ok(L.pmlp_lstm_bwd_wide_jobs(len(wid), wjobs, T, mb, H, P(reset), st), "pmlp_lstm_bwd_wide_jobs")
-        for n in single:
+        if narrow:
+            lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma_jobs(len(narrow), jobs, T, mb, H, P(reset), st),
+                         "pmlp_lstm_bwd_dw_mfma_jobs")
+        for n in fp32:
             r, I = self.rnns[n], self.I[n]
             c0 = hids[n][1].reshape(mb, H)
-            if self.mfma[n]:
-                lstm_seq._ok(L.pmlp_lstm_bwd_dw_mfma(T, mb, H, I, P(r.weight_hh_l0), P(c0), P(reset),
-                                                     P(self.c_out[n]), P(self.gact[n]), P(self.dh[n]), P(self.xh[n]),
-                                                     P(self.lslab[n]), st), "pmlp_lstm_bwd_dw_mfma")
-                continue
             lstm_seq._ok(L.pmlp_lstm_bwd(T, mb, H, P(r.weight_hh_l0), P(c0), P(reset), P(self.c_out[n]),
                                          P(self.gact[n]), P(self.dh[n]), P(self.dgx[n]), st), "pmlp_lstm_bwd")
             dw = lstm_seq._rows_tn(self.dgx[n].view(M, 4 * H), self.xh[n].view(M, I + H + 1))

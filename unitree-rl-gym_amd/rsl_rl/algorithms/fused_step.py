@@ -535,7 +535,7 @@ class RecurrentRollout:
         # both Linear/ELU/Linear heads in one launch (pmlp_heads_forward, fp32) where the
         # fused recurrent step covers the policy; else the torch modules
         from rsl_rl.algorithms import fused_recurrent
-        # the memories' rollout step on the update's matrix-core kernel (pmlp_lstm_step_mfma)
+        # the memories' rollout step on the update's matrix-core kernel (pmlp_lstm_step_mfma_jobs)
         # when the update runs the fused recurrent step with it: the stored log-probabilities
         # then come from the numbers the update recomputes.  Gated on the update's own choice
         # (FusedRecurrentStep.mfma, I + H + 1 <= 128), so both always use the same arithmetic.

@@ -30,7 +30,6 @@ def _lib():
     L = mm.load()
     if not _bound:
         vp, i32 = C.c_void_p, C.c_int32
-        L.pmlp_lstm_last_error.restype = C.c_char_p
         L.pmlp_gru_supported.argtypes = [i32, i32]
         L.pmlp_gru_fwd_jobs.argtypes = [i32, C.POINTER(GruJob), i32, i32, i32, vp, vp]
         L.pmlp_gru_bwd_jobs.argtypes = [i32, C.POINTER(GruJob), i32, i32, i32, vp, vp]
@@ -39,9 +38,7 @@ def _lib():
     return L
 
 
-def _ok(status, what):
-    if status != 0:
-        raise RuntimeError(f"{what} failed: {_lib().pmlp_lstm_last_error().decode(errors='replace')}")
+_ok = lstm_seq._ok  # (one error text for the LSTM, the GRU and the heads: pmlp_lstm_last_error)
 
 
 HIDDEN, MAX_INPUT = 64, 64  # pmlp_gru_supported

@@ -9,8 +9,10 @@ order and (h, c) is zeroed before step t when the env was done at t-1, which is 
 zero state a padded trajectory that starts there begins from.  (The trajectory that
 starts at t = 0 begins from the hidden state saved at t = 0, in both forms.)
 
-``lstm_dense`` is differentiable w.r.t. the four LSTM parameters (autograd Function
-around pmlp_lstm_fwd / pmlp_lstm_bwd plus three GEMMs for the weight gradients);
+``lstm_dense`` is differentiable w.r.t. the four LSTM parameters: an autograd Function
+around the matrix-core kernels at hidden 64 (pmlp_lstm_fwd_mfma_jobs with one job /
+pmlp_lstm_bwd_mfma, or the wide jobs past 64 inputs) and the fp32 kernels otherwise
+(pmlp_lstm_fwd_x / pmlp_lstm_fwd / pmlp_lstm_bwd), plus one product for the weight gradients;
 ``lstm_dense_reference`` is the same recurrence in plain torch ops (CPU, tests).
 """
 import ctypes as C
@@ -23,7 +25,7 @@ _bound = False
 
 
 class LstmJob(C.Structure):
-    """include/ppo_mlp.h pmlp_lstm_job: one memory's sequence in a two-memory launch."""
+    """include/ppo_mlp.h pmlp_lstm_job: one memory's sequence in a launch of 1..2 memories."""
     _fields_ = [("I", C.c_int32), ("x", C.c_void_p), ("w_ih", C.c_void_p), ("b_ih", C.c_void_p),
                 ("b_hh", C.c_void_p), ("w_hh", C.c_void_p), ("h0", C.c_void_p), ("c0", C.c_void_p),
                 ("h_out", C.c_void_p), ("c_out", C.c_void_p), ("gact", C.c_void_p), ("xh", C.c_void_p),
@@ -48,12 +50,9 @@ def _lib():
         L.pmlp_lstm_bwd.argtypes = [i32, i32, i32] + [vp] * 7 + [vp]
         L.pmlp_lstm_fwd_x.argtypes = [i32, i32, i32, i32] + [vp] * 14 + [vp]
         L.pmlp_lstm_step.argtypes = [i32, i32] + [vp] * 6 + [vp]
-        L.pmlp_lstm_fwd_mfma.argtypes = [i32, i32, i32, i32] + [vp] * 12 + [vp]
         L.pmlp_lstm_bwd_mfma.argtypes = [i32, i32, i32] + [vp] * 7 + [vp]
         L.pmlp_lstm_bwd_dw_blocks.argtypes = [i32]
         L.pmlp_lstm_bwd_dw_blocks.restype = i32
-        L.pmlp_lstm_bwd_dw_mfma.argtypes = [i32, i32, i32, i32] + [vp] * 8 + [vp]
-        L.pmlp_lstm_step_mfma.argtypes = [i32, i32, i32] + [vp] * 9 + [vp]
         L.pmlp_lstm_fwd_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, i32, vp, vp]
         L.pmlp_lstm_bwd_dw_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, i32, vp, vp]
         L.pmlp_lstm_step_mfma_jobs.argtypes = [i32, C.POINTER(LstmJob), i32, i32, vp]
@@ -72,7 +71,7 @@ def _ok(status, what):
         raise RuntimeError(f"{what} failed: {_lib().pmlp_lstm_last_error().decode(errors='replace')}")
 
 
-# The update's dense sequences on the matrix cores (pmlp_lstm_fwd_mfma / _bwd_mfma: bf16
+# The dense sequences on the matrix cores (pmlp_lstm_fwd_mfma_jobs / pmlp_lstm_bwd_mfma: split-bf16
 # products, fp32 state) for hidden 64 and inputs <= 64; other shapes take the fp32 kernels.
 def mfma_usable(rnn, x):
     return rnn.hidden_size == 64 and x.shape[-1] <= 64
@@ -139,9 +138,10 @@ class _LSTMDense(torch.autograd.Function):
             ctx.I = I
             return h_out
         if mfma:  # the per-step products on the matrix cores (bf16 operands, fp32 state)
-            _ok(_lib().pmlp_lstm_fwd_mfma(T, B, H, I, p(x), p(w_ih.detach().contiguous()), p(b_ih.detach()),
-                                          p(b_hh.detach()), p(whh), p(h0), p(c0), p(reset), p(h_out), p(c_out),
-                                          p(gact), p(xh), mm._stream()), "pmlp_lstm_fwd_mfma")
+            job = LstmJob(I, p(x), p(w_ih.detach().contiguous()), p(b_ih.detach()), p(b_hh.detach()), p(whh),
+                          p(h0), p(c0), p(h_out), p(c_out), p(gact), p(xh))
+            _ok(_lib().pmlp_lstm_fwd_mfma_jobs(1, C.byref(job), T, B, H, p(reset), mm._stream()),
+                "pmlp_lstm_fwd_mfma_jobs")
         elif I <= 64:  # the input projection inside the sequence kernel, which also writes xh
             _ok(_lib().pmlp_lstm_fwd_x(T, B, H, I, p(x), p(w_ih.detach().contiguous()), p(b_ih.detach()),
                                        p(b_hh.detach()), p(whh), p(h0), p(c0), p(reset), p(h_out), p(c_out), p(gact),
@@ -251,9 +251,11 @@ def lstm_step_(rnn, x, h, c, save=None):
 
 
 def lstm_step_mfma_pair_(steps):
-    """Both memories' rollout step in ONE launch (pmlp_lstm_step_mfma_jobs: the kernel of
-    lstm_step_mfma_ per job, side by side in the grid).  steps: [(rnn, x, h, c, save)] x 2,
-    same batch size.  Returns the h buffers."""
+    """The rollout step of 1..2 hidden-64 memories in ONE launch, in place on the matrix-core
+    kernel (pmlp_lstm_step_mfma_jobs: the update's arithmetic at T = 1, the memories side by
+    side in the grid).  steps: [(rnn, x, h, c, save)] x 1..2, same batch size; h, c [1,B,H]
+    static buffers, read and overwritten; save = (h_dst, c_dst) or None receives the state the
+    step starts from.  Returns the h buffers."""
     p = mm._p
     B = steps[0][1].shape[0]
     jobs = (LstmJob * len(steps))()
@@ -284,17 +286,3 @@ def lstm_step_wide_pair_(steps):
             "pmlp_lstm_step_wide_jobs")
     return [st[2] for st in steps]
 
-
-def lstm_step_mfma_(rnn, x, h, c, save=None):
-    """One rollout step in place on the matrix-core kernel (pmlp_lstm_step_mfma: the update's
-    arithmetic at T = 1, hidden 64): h, c [1,B,H] static buffers; save = (h_dst, c_dst)
-    receives the state the step starts from.  Returns h."""
-    B, I = x.shape
-    H = rnn.hidden_size
-    p = mm._p
-    hs, cs = (None, None) if save is None else save
-    with torch.no_grad():
-        _ok(_lib().pmlp_lstm_step_mfma(B, H, I, p(x), p(rnn.weight_ih_l0), p(rnn.bias_ih_l0), p(rnn.bias_hh_l0),
-                                       p(rnn.weight_hh_l0), p(h), p(c), p(hs), p(cs), mm._stream()),
-            "pmlp_lstm_step_mfma")
-    return h
