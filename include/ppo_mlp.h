@@ -617,4 +617,42 @@ PMLP_API int pmlp_gru_bwd_jobs(int32_t njobs, const pmlp_gru_job* jobs, int32_t 
                                const uint8_t* reset, void* stream);
 PMLP_API int pmlp_gru_step_jobs(int32_t njobs, const pmlp_gru_job* jobs, int32_t B, int32_t H, void* stream);
 
+/* ---- empirical observation normalisation (rsl_rl's EmpiricalNormalization) for the rollout:
+ * running mean and variance of the observation rows, kept in fp64 on the device, applied
+ * through two fp32 tables.  One call per env step takes 1..2 jobs over the same N rows (the
+ * actor's rows and the privileged rows; one job when the critic reads the actor's rows).
+ *   update:  runs when `update` is set and (until < 0 or count < until), tested on the device.
+ *            Batch moments from fp64 sums of d = x - s and d^2 with the shift s = x[0, k]:
+ *            mean_x = s + S1 / N, M2_x = max(S2 - S1^2 / N, 0) (a constant column gives
+ *            mean_x = s and M2_x = 0 exactly).  Merge, in fp64: n' = count + N, r = N / n',
+ *            delta = mean_x - mean, mean' = mean + delta r,
+ *            var' = (var count + M2_x + delta^2 count r) / n', count' = n'.
+ *            No floating-point atomics; partials are combined in block-index order, so the
+ *            result does not depend on the order in which blocks run.
+ *   tables:  mean32 = (float) mean', inv32 = (float) (1 / (sqrt(var') + eps)) (fp64 inside);
+ *            with the update off they are recomputed from the state as it stands.
+ *   rows:    y = (x - mean32) * inv32 in fp32, two roundings, with this call's tables (update
+ *            first, then apply).  Nothing outside [N, D] of y is written.
+ * At most two launches per call (one with `update` 0).  `scratch` (pmlp_obs_norm_scratch_bytes(D)
+ * bytes, 8-byte aligned, one per job) is allocated once by the caller and needs no resetting
+ * between calls, so a captured graph replays the call.  Any ldx, ldy >= D; any N >= 1;
+ * D <= PMLP_OBS_NORM_MAX_D.  Errors (text in pmlp_obs_norm_last_error), all before any launch:
+ * -1 bad argument, -2 D past what is built, -3 null state or scratch, -4 y overlaps x.       */
+#define PMLP_OBS_NORM_MAX_D 1024
+#define PMLP_OBS_NORM_MAX_PARTS 32
+typedef struct pmlp_obs_norm_job {
+    const float* x; /* raw rows [N, D], row stride ldx (read only: never aliased by y) */
+    float* y;       /* normalised rows [N, D], row stride ldy                          */
+    int32_t D, ldx, ldy;
+    int64_t* count; /* state: rows seen                                                */
+    double *mean, *var;     /* state [D]                                               */
+    float *mean32, *inv32;  /* tables [D], written by every call                       */
+    void* scratch;
+} pmlp_obs_norm_job;
+PMLP_API const char* pmlp_obs_norm_last_error(void);
+PMLP_API int32_t pmlp_obs_norm_max_width(void);
+PMLP_API int64_t pmlp_obs_norm_scratch_bytes(int32_t D);
+PMLP_API int pmlp_obs_norm_step(int32_t njobs, const pmlp_obs_norm_job* jobs, int32_t N, int32_t update,
+                                int64_t until, double eps, void* stream);
+
 #endif

@@ -232,6 +232,11 @@ class LeggedRobotCfgPPO(BaseConfig):
         num_steps_per_env = 24
         max_iterations = 1500
         save_interval = 50
+        # running mean / variance of the observation rows, applied before the policy and the
+        # critic see them (rsl_rl's EmpiricalNormalization); `_until`: rows after which the
+        # statistics freeze (None: never)
+        empirical_normalization = False
+        empirical_normalization_until = None
         experiment_name = "test"
         run_name = ""
         resume = False

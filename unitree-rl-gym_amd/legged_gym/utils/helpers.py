@@ -129,7 +129,32 @@ def export_policy_as_jit(actor_critic, path):
         return
     os.makedirs(path, exist_ok=True)
     model = _plain_linear(copy.deepcopy(actor_critic.actor).to("cpu"))
+    if getattr(actor_critic, "obs_normalizer", None) is not None:
+        # empirical_normalization: the exported module takes raw env rows, as act_inference does
+        model = torch.nn.Sequential(_obs_norm(actor_critic), *model)
     torch.jit.script(model).save(os.path.join(path, "policy_1.pt"))
+
+
+class TableNorm(torch.nn.Module):
+    """A frozen EmpiricalNormalization baked into an exported policy: y = (x - mean32) * inv32
+    with the fp32 tables of the normaliser's state at export time."""
+
+    def __init__(self, mean32, inv32):
+        super().__init__()
+        self.register_buffer("mean32", mean32.detach().clone().cpu())
+        self.register_buffer("inv32", inv32.detach().clone().cpu())
+
+    def forward(self, x):
+        return (x - self.mean32) * self.inv32
+
+
+def _obs_norm(actor_critic):
+    """The actor-critic's `obs_normalizer` as a TableNorm (Identity when it has none)."""
+    norm = getattr(actor_critic, "obs_normalizer", None)
+    if norm is None:
+        return torch.nn.Identity()
+    from rsl_rl.modules.normalizer import tables
+    return TableNorm(*tables(norm._mean[0], norm._var[0], norm.eps))
 
 
 def _plain_linear(module):
@@ -156,11 +181,12 @@ class PolicyExporterLSTM(torch.nn.Module):
         self.is_recurrent = actor_critic.is_recurrent
         self.memory = copy.deepcopy(actor_critic.memory_a.rnn)
         self.memory.cpu()
+        self.obs_norm = _obs_norm(actor_critic)
         self.register_buffer("hidden_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
         self.register_buffer("cell_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
 
     def forward(self, x):
-        out, (h, c) = self.memory(x.unsqueeze(0), (self.hidden_state, self.cell_state))
+        out, (h, c) = self.memory(self.obs_norm(x).unsqueeze(0), (self.hidden_state, self.cell_state))
         self.hidden_state[:] = h
         self.cell_state[:] = c
         return self.actor(out.squeeze(0))
@@ -186,10 +212,11 @@ class PolicyExporterGRU(torch.nn.Module):
         self.is_recurrent = actor_critic.is_recurrent
         self.memory = copy.deepcopy(actor_critic.memory_a.rnn)
         self.memory.cpu()
+        self.obs_norm = _obs_norm(actor_critic)
         self.register_buffer("hidden_state", torch.zeros(self.memory.num_layers, 1, self.memory.hidden_size))
 
     def forward(self, x):
-        out, h = self.memory(x.unsqueeze(0), self.hidden_state)
+        out, h = self.memory(self.obs_norm(x).unsqueeze(0), self.hidden_state)
         self.hidden_state[:] = h
         return self.actor(out.squeeze(0))
 

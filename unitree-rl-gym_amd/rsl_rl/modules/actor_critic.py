@@ -120,8 +120,14 @@ class ActorCritic(nn.Module):
         with torch.no_grad():
             return mean + std * torch.randn_like(mean), value
 
+    def _normalized(self, observations):
+        """Raw env rows -> what the actor was trained on: the runner's `obs_normalizer`
+        (cfg `empirical_normalization`), frozen; absent, the rows as they are."""
+        norm = getattr(self, "obs_normalizer", None)
+        return observations if norm is None else norm.frozen(observations)
+
     def act_inference(self, observations):
-        return self._run(self.actor, observations)
+        return self._run(self.actor, self._normalized(observations))
 
     def evaluate(self, critic_observations, **kwargs):
         return self._run(self.critic, critic_observations)

@@ -36,8 +36,8 @@ class ActorCriticRecurrent(ActorCritic):
         return super().act(input_a.squeeze(0))
 
     def act_inference(self, observations):
-        input_a = self.memory_a(observations)
-        return super().act_inference(input_a.squeeze(0))
+        input_a = self.memory_a(self._normalized(observations))
+        return self._run(self.actor, input_a.squeeze(0))
 
     def evaluate(self, critic_observations, masks=None, hidden_states=None):
         input_c = self.memory_c(critic_observations, masks, hidden_states)

@@ -110,6 +110,13 @@ class HeadAct(C.Structure):
                 ("st_cobs", C.c_void_p)]
 
 
+class ObsNormJob(C.Structure):
+    """include/ppo_mlp.h pmlp_obs_norm_job (pmlp_obs_norm_step)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("D", C.c_int32), ("ldx", C.c_int32), ("ldy", C.c_int32),
+                ("count", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p), ("mean32", C.c_void_p),
+                ("inv32", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 MAX_JOBS, MAX_GEMM_JOBS = 16, 4
 PMLP_MAX_MIRROR = 8  # include/ppo_mlp.h: bf16 weight copies one Adam launch writes
 
@@ -174,6 +181,11 @@ def load():
         L.pmlp_heads_forward.argtypes = [i32, C.POINTER(HeadJob), i32, i32, vp]
         L.pmlp_heads_backward.argtypes = [i32, C.POINTER(HeadJob), i32, i32, vp]
         L.pmlp_heads_forward_act.argtypes = [C.POINTER(HeadJob), i32, i32, C.POINTER(HeadAct), vp]
+        L.pmlp_obs_norm_last_error.restype = C.c_char_p
+        L.pmlp_obs_norm_max_width.restype = i32
+        L.pmlp_obs_norm_scratch_bytes.argtypes = [i32]
+        L.pmlp_obs_norm_scratch_bytes.restype = i64
+        L.pmlp_obs_norm_step.argtypes = [i32, C.POINTER(ObsNormJob), i32, i32, i64, C.c_double, vp]
         _lib = L
     return _lib
 
@@ -307,6 +319,21 @@ def _gemm(epi, jobs, ksplit=0):
     gradient)."""
     arr = (GemmJob * len(jobs))(*[_gemm_job(j) for j in jobs])
     _ok(load().pmlp_gemm(epi, len(jobs), arr, ksplit, _stream()), "pmlp_gemm")
+
+
+def obs_norm_step(jobs, N, update, until, eps):
+    """pmlp_obs_norm_step: jobs = 1..2 dicts x (fp32 rows, stride(0) >= D), y, D, count (int64),
+    mean, var (fp64 [D]), mean32, inv32 (fp32 [D]), scratch (pmlp_obs_norm_scratch_bytes(D) bytes),
+    all over the same N rows.  The running moments are updated where `update` and (until < 0
+    or count < until); y = (x - mean32) * inv32 with the tables of this call."""
+    arr = (ObsNormJob * len(jobs))(*[ObsNormJob(_p(j["x"]), _p(j["y"]), j["D"], j["x"].stride(0), j["y"].stride(0),
+                                                _p(j["count"]), _p(j["mean"]), _p(j["var"]), _p(j["mean32"]),
+                                                _p(j["inv32"]), _p(j["scratch"])) for j in jobs])
+    status = load().pmlp_obs_norm_step(len(jobs), arr, int(N), int(bool(update)), -1 if until is None else int(until),
+                                       float(eps), _stream())
+    if status != 0:
+        raise RuntimeError(f"pmlp_obs_norm_step failed ({status}): "
+                           f"{load().pmlp_obs_norm_last_error().decode(errors='replace')}")
 
 
 def permutation_(out):

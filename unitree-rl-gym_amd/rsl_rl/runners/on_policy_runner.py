@@ -13,6 +13,7 @@ import torch.distributed as dist
 from rsl_rl.algorithms import PPO  # noqa: F401  (eval'd by name)
 from rsl_rl.env import VecEnv
 from rsl_rl.modules import ActorCritic, ActorCriticRecurrent  # noqa: F401  (eval'd by name)
+from rsl_rl.modules.normalizer import EmpiricalNormalization, normalize_pair
 from rsl_rl.utils import capture_without_gc
 
 
@@ -132,6 +133,9 @@ class OnPolicyRunner:
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs],
                               [self.env.num_privileged_obs], [self.env.num_actions])
+        self.obs_normalizer = self.critic_obs_normalizer = None
+        if self.cfg.get("empirical_normalization", False):
+            self._build_normalizers(actor_critic, num_critic_obs)
         self.is_main = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
         self.log_dir = log_dir if self.is_main else None
         self.writer = None
@@ -156,6 +160,12 @@ class OnPolicyRunner:
         critic_obs = privileged_obs if privileged_obs is not None else obs
         obs, critic_obs = obs.to(self.device), critic_obs.to(self.device)
         self.alg.actor_critic.train()
+        if self.obs_normalizer is not None:
+            # the rows the env holds at the start: normalised with the state as it stands and not
+            # counted (every later row is counted once, when env.step returns it; rsl_rl 2.x
+            # hands these first rows to the policy raw)
+            obs, critic_obs = normalize_pair(self.obs_normalizer, obs, self.critic_obs_normalizer, critic_obs,
+                                             frozen=True)
 
         ep_infos = []
         rewbuffer = deque(maxlen=100)
@@ -251,8 +261,31 @@ class OnPolicyRunner:
         critic_obs = privileged_obs if privileged_obs is not None else obs
         obs, critic_obs, rewards, dones = (obs.to(self.device), critic_obs.to(self.device),
                                            rewards.to(self.device), dones.to(self.device))
+        if self.obs_normalizer is not None:
+            # update, then normalise (one native call for both row sets): the next act, the
+            # storage rows it writes and compute_returns all see normalised rows
+            obs, critic_obs = normalize_pair(self.obs_normalizer, obs, self.critic_obs_normalizer, critic_obs)
         self.alg.process_env_step(rewards, dones, infos)
         return obs, critic_obs, rewards, dones, infos
+
+    def _build_normalizers(self, actor_critic, num_critic_obs):
+        """Runner cfg `empirical_normalization`: EmpiricalNormalization modules registered on the
+        actor-critic as `obs_normalizer` and `critic_obs_normalizer` (one module under both names
+        when there are no privileged observations), so the model state dict carries them and
+        act_inference applies the actor's.  They hold buffers only: parameters(), and with it
+        the optimizer and the fused steps' flat parameter set, are unchanged."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("empirical_normalization is per-process: with torch.distributed world size > 1 "
+                             "the ranks' statistics, and so their policies, would differ")
+        until = self.cfg.get("empirical_normalization_until", None)
+        self.obs_normalizer = EmpiricalNormalization([self.env.num_obs], until=until).to(self.device)
+        if self.env.num_privileged_obs is not None:
+            self.critic_obs_normalizer = EmpiricalNormalization([num_critic_obs], until=until).to(self.device)
+        else:
+            self.critic_obs_normalizer = self.obs_normalizer
+        actor_critic.obs_normalizer = self.obs_normalizer
+        actor_critic.critic_obs_normalizer = self.critic_obs_normalizer
+        assert not list(self.obs_normalizer.parameters()) and not list(self.critic_obs_normalizer.parameters())
 
     def _capture_rollout(self, obs, critic_obs, cur_reward_sum, cur_episode_length):
         """_RolloutGraph, or None when the loop cannot be captured (e.g. a task's Python step
