@@ -370,9 +370,10 @@ typedef struct lgs_actuator_rand {
  * after the handstand's contact-flag flip and after clip_observations, so the history holds what
  * the policy was shown.  frame(t) uses noise_vec[0 .. F) and LGS_STREAM_NOISE draws 0 .. F)
  * (the handstand's flips F + j), exactly as without the call: no draw moves, none is added, and
- * older frames are copied, never re-noised.  The privileged row is untouched in every layout
- * (the humanoid's P entries; the handstand's P = F noisy frame; the quadruped has none, so its
- * critic reads the history row).  Everything else the step writes -- rewards, termination,
+ * older frames are copied, never re-noised.  The privileged row has no history in any layout
+ * (the humanoid's P entries; the handstand's P = F noisy frame; the quadruped's one clean frame
+ * under lgs_priv_params below, and no row without it: its critic then reads the history row).
+ * Everything else the step writes -- rewards, termination,
  * resets, episode sums, commands, the last_* bookkeeping, the state -- is bit for bit what it
  * writes without the call.
  * Episode boundary: the first row an env writes after any reset of that env -- the reset inside
@@ -410,6 +411,49 @@ typedef struct lgs_obs_history {
     float*   history;    /* device [N, (H-1) * F] */
     int32_t* fill;       /* device [N] */
 } lgs_obs_history;
+
+/* ---- the randomised parameters in the privileged row (lgs_set_privileged_parameters) ----
+ * The asymmetric critic's row: during training the critic may see the simulator's own truth,
+ * the numbers that were randomised included.  With D the model's real DOFs, S the scan points in
+ * the rows (0 without lgs_height_obs), F the quadruped layout's own frame width 12 + 3 A, and
+ *   Wp = 2 + (3 D + 1)  with lgs_actuator_rand enabled,   Wp = 2  without,
+ * enabled = 1 puts a parameter tail of Wp entries into the privileged row of env e, in this order:
+ *   1   shape_friction[e] of lgs_set_env_properties (as the substep reads it)   group friction
+ *   1   added_base_mass[e] (0 when never set)                                   group added_mass
+ *   D   kp_scale[e][j]                                                          group kp
+ *   D   kd_scale[e][j]                                                          group kd
+ *   D   strength[e][j]                                                          group strength
+ *   1   (float) delay[e]                                                        group delay
+ * each  clip((v - offset) * scale, -clip_observations, clip_observations)  in fp32 without
+ * contraction, {offset, scale} its group's.  No tail entry gets noise; no random draw is added
+ * or moved.  The last four groups exist only with the actuator rows.
+ *   LGS_OBS_QUADRUPED  num_privileged_obs = F + Wp + S, the row [clean frame | tail | clean scan]:
+ *       the clean frame is the F values of the observation stage before the noise, clipped -- bit
+ *       for bit what the same step writes to the newest frame of obs with add_noise = 0; the clean
+ *       scan is clip(h, -clip_observations, clip_observations), the humanoid's rule.  With an
+ *       observation history the privileged row still holds one frame.
+ *   LGS_OBS_HUMANOID   num_privileged_obs = (14 + 3 A) + Wp + S, the row [head | tail | scan]: the
+ *       head and the scan entries keep their bits, the scan only moves by Wp.
+ *   LGS_OBS_HANDSTAND  refused: its privileged row is the reference's noisy frame by definition.
+ * Limit: head + Wp <= LGS_MAX_OBS (a G1 with 23 DOFs and the actuator rows: 83 + 72 does not fit);
+ * the row as a whole stays within what lgs_set_task accepts.
+ * An env that resets shows the rows its NEXT control step acts on -- the redrawn ones
+ * (lgs_actuator_rand's resample_on_reset), not those the ending step ran on: the privileged row
+ * written after a reset is the first row of the new episode.  That holds for the reset inside a
+ * control step (whose row is written by the same launch), and for lgs_reset_idx (mask bytes 1
+ * and 2) and lgs_reset_all (whose rows the following step writes).
+ * Everything else a step writes -- obs, rewards, termination, state, episode sums, the last_*
+ * rows, the actuator rows, the history buffers, the extras -- is bit for bit what it writes
+ * without the call; lgs_post_physics_finish and lgs_step_deferred write the same row as lgs_step.
+ * This call, lgs_set_task and the other setters may come in any order: every step / reset entry
+ * point checks them together -- the layout, finite offsets and scales, head + Wp <= LGS_MAX_OBS,
+ * num_privileged_obs == head + Wp + S (the message names the width it would have to be), a
+ * non-NULL env->priv_obs for a step -- and refuses with LGS_ERR_ARG before any launch. */
+typedef struct lgs_priv_params {
+    int32_t enabled;   /* 0: every row is what it is without this call */
+    /* {offset, scale} per group: entry = (value - offset) * scale */
+    float friction[2], added_mass[2], kp[2], kd[2], strength[2], delay[2];
+} lgs_priv_params;
 
 /* ---- per-env buffers of the VecEnv (device pointers; torch owns them) ---- */
 typedef struct lgs_env_buffers {
@@ -581,6 +625,10 @@ LGS_API int lgs_set_actuator_randomization(lgs_sim* sim, const lgs_actuator_rand
 /* the last `frames` observation frames as the policy row (lgs_obs_history above).
  * desc->enabled = 0 turns it off; a NULL sim or desc is an error. */
 LGS_API int lgs_set_observation_history(lgs_sim* sim, const lgs_obs_history* desc);
+
+/* the randomised parameters as a tail of the privileged row (lgs_priv_params above).
+ * desc->enabled = 0 turns it off; a NULL sim or desc is an error. */
+LGS_API int lgs_set_privileged_parameters(lgs_sim* sim, const lgs_priv_params* desc);
 
 /* create_actor(..., self_collisions, 0) (legged_robot.py:373-374): the self-collision
  * proxies and pairs of every env (host descriptor, copied; NULL or num_pairs = 0: off) */

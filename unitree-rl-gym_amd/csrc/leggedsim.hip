@@ -2229,8 +2229,50 @@ static_assert(sizeof(ActuatorTail) % alignof(ObsHistTail) == 0, "ObsHistTail fol
 __device__ __forceinline__ const ObsHistTail& obs_hist_tail(const lgs_task_params& T) {
     return *reinterpret_cast<const ObsHistTail*>(&actuator_tail(T) + 1);
 }
+
+// ---- the randomised parameters in the privileged row (include/leggedsim.h, lgs_priv_params) ----
+// The sim's own per-env friction and added-mass rows (DevState's, which the post-physics stages
+// must not reach through the kernel argument) and the groups' {offset, scale}, in device memory
+// after ObsHistTail and for its reason; written by lgs_set_privileged_parameters alone.  The
+// actuator rows are ActuatorTail's.
+enum { PRIV_FRICTION = 0, PRIV_MASS, PRIV_KP, PRIV_KD, PRIV_STRENGTH, PRIV_DELAY, PRIV_GROUPS };
+struct PrivTail {
+    const float* friction;    // [N] lgs_set_env_properties' shape friction, as the substep reads it
+    const float* added_mass;  // [N]
+    int enabled, pad_;
+    float offset[PRIV_GROUPS], scale[PRIV_GROUPS];
+};
+static_assert(sizeof(ObsHistTail) % alignof(PrivTail) == 0, "PrivTail follows ObsHistTail");
+__device__ __forceinline__ const PrivTail& priv_tail(const lgs_task_params& T) {
+    return *reinterpret_cast<const PrivTail*>(&obs_hist_tail(T) + 1);
+}
 constexpr size_t TASK_BLOCK_BYTES =
-    sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail) + sizeof(ObsHistTail);
+    sizeof(lgs_task_params) + sizeof(TerrainTail) + sizeof(ActuatorTail) + sizeof(ObsHistTail) + sizeof(PrivTail);
+
+// Entry k of the parameter tail of env e, before the group's {offset, scale}: friction, added
+// mass, then (with the actuator rows, A = the model's DOFs) kp, kd and strength per DOF and the
+// delay.  `redrawn`: this launch reset the env and resample_actuator redrew its rows from other
+// lanes; the reading lane repeats the draw (philox_uniform is pure: the same bits) and reads
+// no store of this launch back.  Returns the group through *g.
+__device__ __forceinline__ float priv_tail_value(const lgs_task_params& T, const PrivTail& X, int e, uint32_t step,
+                                                 int k, bool redrawn, int* g) {
+    if (k < 2) { *g = k; return k == 0 ? X.friction[e] : X.added_mass[e]; }
+    const ActuatorTail& R = actuator_tail(T);
+    const int A = T.num_actions;
+    const int j = k - 2;
+    if (j == 3 * A) {
+        *g = PRIV_DELAY;
+        if (!redrawn) return (float)R.delay[e];
+        const int n = R.dl_hi - R.dl_lo + 1;
+        return (float)(R.dl_lo + min((int)(philox_uniform(T.seed, e, step, LGS_STREAM_ACTUATOR, 3 * LGS_MAX_DOFS) * (float)n), n - 1));
+    }
+    const int grp = j / A, d = j - grp * A;
+    *g = PRIV_KP + grp;
+    if (!redrawn) return (grp == 0 ? R.kp_scale : grp == 1 ? R.kd_scale : R.strength)[(size_t)A * e + d];
+    const float lo = grp == 0 ? R.kp_lo : grp == 1 ? R.kd_lo : R.st_lo;
+    const float hi = grp == 0 ? R.kp_hi : grp == 1 ? R.kd_hi : R.st_hi;
+    return rand_range(lo, hi, philox_uniform(T.seed, e, step, LGS_STREAM_ACTUATOR, grp * LGS_MAX_DOFS + d));
+}
 
 // Entry j of the newest frame is c: the row's older slots and the env's new history, slot by
 // slot (two values live).  old[s] = the env's history slot s as the step found it, frames
@@ -2754,9 +2796,31 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         if (Hn > 1) obs_history_entry(row, obs_hist_tail(T).history + (size_t)newest * e, F, Hn, i, c, live);
     }
     if (Hn > 1 && lane == 0) obs_hist_tail(T).fill[e] = 1;  // (lane 0 alone reads and writes the flag)
-    if (P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID)
-        for (int i = lane; i < P - S; i += WAVE / EPW)
+    // the randomised parameters in the privileged row (lgs_priv_params): [head | tail | scan], Wp
+    // tail entries, 0 without it (wave-uniform).  The descriptor's block is a cold line like the
+    // history's: a privileged row as wide as the layout's own (none for the quadruped), known from
+    // the task's hot fields, has no tail and does not look.  The entry points hold P to
+    // head + Wp + S before any launch.
+    const bool hum = T.obs_layout == LGS_OBS_HUMANOID;
+    const bool ptail = P > 0 && E.priv_obs && T.obs_layout != LGS_OBS_HANDSTAND &&
+                       P - S != (hum ? 14 + 3 * Ad : 0) && priv_tail(T).enabled;
+    const int Wp = ptail ? 2 + (actuator_tail(T).enabled ? 3 * A + 1 : 0) : 0;
+    const int Hp = P - S - Wp;  // the head: the humanoid's own; the quadruped's clean frame (obs_tmp[0 .. F))
+    if (P > 0 && E.priv_obs && (hum || ptail))
+        for (int i = lane; i < Hp; i += WAVE / EPW)
             E.priv_obs[(size_t)P * e + i] = clipf(s.u.post.obs_tmp[i], -T.clip_observations, T.clip_observations);
+    if (ptail) {
+        // one lane per entry, from the global rows straight to the row; an env this step reset
+        // shows the rows its next step acts on (priv_tail_value)
+        const PrivTail& X = priv_tail(T);
+        const bool redrawn = reset && actuator_tail(T).resample;
+        for (int k = lane; k < Wp; k += WAVE / EPW) {
+            int g;
+            const float v = priv_tail_value(T, X, e, step, k, redrawn, &g);
+            E.priv_obs[(size_t)P * e + Hp + k] =
+                clipf((v - X.offset[g]) * X.scale[g], -T.clip_observations, T.clip_observations);
+        }
+    }
     if (S > 0) {
         // legged_gym's compute_observations tail (include/leggedsim.h, lgs_height_obs): the scan
         // the prepare part measured before the reset against the root after it, straight from
@@ -2765,7 +2829,7 @@ __device__ void post_physics(Smem<D, B, ROWS>& s, const lgs_task_params& T, cons
         const TerrainTail& X = terrain_tail(T);
         const float* mh = X.heights + (size_t)S * e;
         const float rz = s.root[2] - X.obs_offset;
-        const bool priv = P > 0 && E.priv_obs && T.obs_layout == LGS_OBS_HUMANOID;
+        const bool priv = P > 0 && E.priv_obs && (hum || ptail);
         for (int k = lane; k < S; k += WAVE / EPW) {
             const float h = clipf(rz - mh[k], -X.obs_clip, X.obs_clip) * X.obs_scale;
             float x = h;
@@ -3063,6 +3127,7 @@ struct lgs_sim {
     int task_decimation = 0;     // the task's decimation: the action delay's upper bound
     lgs_obs_history ohist{};     // lgs_set_observation_history's descriptor (check_obs_width)
     int task_feet = 0;           // the task's feet: part of the handstand layout's row
+    lgs_priv_params priv{};      // lgs_set_privileged_parameters' descriptor (check_priv_params)
     int epw = 1;    // envs per wave of k_step (2 for a 32-row entry at even N)
     std::vector<std::string> body_names, dof_names;  // name queries (empty when not given)
 };
@@ -3379,7 +3444,7 @@ LGS_API int lgs_create_sim(const lgs_model_desc* m, const lgs_sim_params* p, int
         free(ones);
     }
     static_assert(sizeof(lgs_task_params) % alignof(TerrainTail) == 0, "TerrainTail follows lgs_task_params");
-    // (the task, then the three device blocks its kernels read through its pointer)
+    // (the task, then the four device blocks its kernels read through its pointer)
     HIP_TRY(hipMalloc(&s->task_dev, TASK_BLOCK_BYTES));
     HIP_TRY(hipMemset(s->task_dev, 0, TASK_BLOCK_BYTES));
     *out = s;
@@ -3659,6 +3724,34 @@ LGS_API int lgs_set_observation_history(lgs_sim* s, const lgs_obs_history* d) {
     return LGS_OK;
 }
 
+static bool priv_params_finite(const lgs_priv_params& p) {
+    for (const float* g : {p.friction, p.added_mass, p.kp, p.kd, p.strength, p.delay})
+        if (!(fabsf(g[0]) <= FLT_MAX) || !(fabsf(g[1]) <= FLT_MAX)) return false;
+    return true;
+}
+
+LGS_API int lgs_set_privileged_parameters(lgs_sim* s, const lgs_priv_params* d) {
+    if (!s || !d) return set_err(LGS_ERR_ARG, "lgs_set_privileged_parameters: null argument");
+    lgs_priv_params v{};
+    if (d->enabled) {
+        v = *d;
+        v.enabled = 1;
+    }
+    // (as with the history: a descriptor the entry points will refuse never reaches the device as
+    // enabled; the widths are theirs to check, check_priv_params)
+    PrivTail t{};
+    if (v.enabled && priv_params_finite(v)) {
+        t.friction = s->friction; t.added_mass = s->added_mass; t.enabled = 1;
+        const float* groups[PRIV_GROUPS] = {v.friction, v.added_mass, v.kp, v.kd, v.strength, v.delay};
+        for (int g = 0; g < PRIV_GROUPS; ++g) { t.offset[g] = groups[g][0]; t.scale[g] = groups[g][1]; }
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));  // no step may still read the previous block
+    HIP_TRY(hipMemcpy(reinterpret_cast<char*>(s->task_dev + 1) + sizeof(TerrainTail) + sizeof(ActuatorTail) +
+                      sizeof(ObsHistTail), &t, sizeof(t), hipMemcpyHostToDevice));
+    s->priv = v;
+    return LGS_OK;
+}
+
 // The actuator descriptor against the task (the two setters may come in either order, so every
 // step / reset entry point checks the pair before it launches anything): a kernel never sees a
 // NULL buffer, a range it cannot draw from or a delay past the decimation loop.
@@ -3710,17 +3803,51 @@ static int check_obs_history(lgs_sim* s, const char* what) {
                            (P < 1 ? std::string() : " (" + std::to_string(P) + ") = " + std::to_string(h.frames * head + P)));
         return LGS_OK;  // (the scan's own limits, the layout and the privileged row: check_obs_width)
     }
-    if (head > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS || s->task_obs != h.frames * head)
+    if (head > LGS_MAX_OBS || (!s->priv.enabled && s->task_priv > LGS_MAX_OBS) || s->task_obs != h.frames * head)
         return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " is not " +
                        std::to_string(h.frames) + " frames of the layout's head (" + std::to_string(head) + ")");
     return LGS_OK;
 }
 
+// The privileged row against lgs_set_privileged_parameters (a setter of the same kind: any order
+// with the others, so the entry points check): with the descriptor on the row is exactly the
+// layout's privileged head (the quadruped's clean frame), the parameter tail and the scan's
+// points, and the head and the tail together fit LGS_MAX_OBS.  The other checks' own rules for
+// the privileged row (the quadruped's LGS_MAX_OBS bound, the humanoid's head + scan) give way
+// to this one when the descriptor is on, and only then.
+static int check_priv_params(lgs_sim* s, const char* what) {
+    const lgs_priv_params& p = s->priv;
+    if (!p.enabled) return LGS_OK;
+    const std::string w = std::string(what) + ": privileged parameters: ";
+    if (s->task_layout != LGS_OBS_QUADRUPED && s->task_layout != LGS_OBS_HUMANOID)
+        return set_err(LGS_ERR_ARG, w + "the handstand layout's privileged row is its noisy frame (quadruped or humanoid layout only)");
+    if (!priv_params_finite(p)) return set_err(LGS_ERR_ARG, w + "every group needs a finite offset and scale");
+    const int A = s->task_actions;
+    const int head = s->task_layout == LGS_OBS_HUMANOID ? 14 + 3 * A : 12 + 3 * A;
+    const int Wp = 2 + (s->act.enabled ? 3 * A + 1 : 0);
+    const int S = s->hobs.enabled ? s->task_scan : 0;
+    if (head + Wp > LGS_MAX_OBS)
+        return set_err(LGS_ERR_ARG, w + "the head (" + std::to_string(head) + ") + the parameter tail (" + std::to_string(Wp) +
+                       ") = " + std::to_string(head + Wp) + " exceed LGS_MAX_OBS (" + std::to_string(LGS_MAX_OBS) + ")");
+    if (s->task_priv != head + Wp + S)
+        return set_err(LGS_ERR_ARG, w + "num_privileged_obs is " + std::to_string(s->task_priv) + ", the row is the head (" +
+                       std::to_string(head) + ") + the parameter tail (" + std::to_string(Wp) + ") + " + std::to_string(S) +
+                       " scan points = " + std::to_string(head + Wp + S));
+    return LGS_OK;
+}
+
+static int check_obs_rows(lgs_sim* s, const char* what);
 static int check_obs_width(lgs_sim* s, const char* what) {
+    if (const int rc = check_obs_rows(s, what)) return rc;
+    return check_priv_params(s, what);
+}
+
+static int check_obs_rows(lgs_sim* s, const char* what) {
     if (const int rc = check_obs_history(s, what)) return rc;
+    const bool ptail = s->priv.enabled != 0;  // (the privileged row's width: check_priv_params)
     if (!s->hobs.enabled) {
         if (s->ohist.enabled) return LGS_OK;  // (the rows are frames of the head: checked above)
-        if (s->task_obs > LGS_MAX_OBS || s->task_priv > LGS_MAX_OBS)
+        if (s->task_obs > LGS_MAX_OBS || (!ptail && s->task_priv > LGS_MAX_OBS))
             return set_err(LGS_ERR_ARG, std::string(what) + ": obs counts exceed LGS_MAX_OBS (no height observations set)");
         return LGS_OK;
     }
@@ -3733,8 +3860,8 @@ static int check_obs_width(lgs_sim* s, const char* what) {
     const bool hum = s->task_layout == LGS_OBS_HUMANOID;
     const int head = hum ? 11 + 3 * A : 12 + 3 * A, head_priv = 14 + 3 * A;
     const int frames = s->ohist.enabled ? s->ohist.frames : 1;  // (the privileged row has no history)
-    if (head_priv > LGS_MAX_OBS || s->task_obs != frames * head + P || (hum && s->task_priv != 0 && s->task_priv != head_priv + P) ||
-        (!hum && s->task_priv > LGS_MAX_OBS))
+    if (head_priv > LGS_MAX_OBS || s->task_obs != frames * head + P || (hum && !ptail && s->task_priv != 0 && s->task_priv != head_priv + P) ||
+        (!hum && !ptail && s->task_priv > LGS_MAX_OBS))
         return set_err(LGS_ERR_ARG, std::string(what) + ": num_obs " + std::to_string(s->task_obs) + " / num_privileged_obs " +
                        std::to_string(s->task_priv) + " do not match " + (frames > 1 ? std::to_string(frames) + " frames of " : std::string()) +
                        "the layout's head (" + std::to_string(head) +
@@ -3774,6 +3901,8 @@ static int check_terrain_buffers(lgs_sim* s, const lgs_env_buffers* env, const c
     if (const int rc = check_obs_width(s, what)) return rc;
     if (s->task_curriculum && (!env->terrain_levels || !env->terrain_types || !env->terrain_origins))
         return set_err(LGS_ERR_ARG, std::string(what) + ": terrain_curriculum needs terrain_levels, terrain_types, terrain_origins");
+    if (s->priv.enabled && !env->priv_obs)
+        return set_err(LGS_ERR_ARG, std::string(what) + ": privileged parameters need the priv_obs buffer");
     if (s->task_heights && !env->measured_heights)
         return set_err(LGS_ERR_ARG, std::string(what) + ": measure_heights needs the measured_heights buffer");
     return sync_terrain_tail(s, env);

@@ -31,7 +31,7 @@ from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
 from leggedsim.task import (actuator_rand_params, build_task_params, check_scan_observations, height_obs_params,
-                            obs_history_params, terrain_switches)
+                            obs_history_params, priv_params, terrain_switches)
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -481,6 +481,7 @@ class LeggedRobot(BaseTask):
         self.sim.set_height_observations(self.height_obs)
         self._build_actuator_randomization()
         self._build_observation_history()
+        self._build_privileged_parameters()
         self._env_structs = [self._make_env_struct(i) for i in range(2)]
         self._bound = {name: getattr(self, name) for name in self.CALLBACK_BUFFERS}
         self._split_step = bool(self._py_rewards or self._hooks)
@@ -524,6 +525,17 @@ class LeggedRobot(BaseTask):
             self._obs_history_fill = torch.zeros(N, dtype=torch.int32, device=dev)
             R.history, R.fill = self.obs_history.data_ptr(), self._obs_history_fill.data_ptr()
             self.sim.set_observation_history(R, (self.obs_history, self._obs_history_fill))
+
+    def _build_privileged_parameters(self):
+        """cfg.env.privileged_parameters: the privileged row the critic reads carries
+        the randomised parameters -- [clean frame | friction, added mass, kp, kd, strength, delay |
+        clean scan] for the quadruped layout, the humanoid's own head in the frame's place -- written
+        by the native step's observation stage into privileged_obs_buf.  num_priv_tail is the
+        tail's width, 0 when off."""
+        self.priv_params = priv_params(self)
+        self.num_priv_tail = self.priv_params.num_tail
+        if self.priv_params.enabled:
+            self.sim.set_privileged_parameters(self.priv_params)
 
     def _make_env_struct(self, i):
         E = cabi.EnvBuffers()

@@ -12,6 +12,12 @@ class LeggedRobotCfg(BaseConfig):
         # oldest first, built inside the native step (an episode's first row repeats its frame);
         # num_observations is then H x the layout's own width.  1: off.
         history_length = 1
+        # privileged_parameters: the privileged (critic) row carries the randomised
+        # parameters -- shape friction, added base mass and, with the actuator randomisation on, the
+        # per-DOF kp / kd / strength factors and the action delay -- each mapped to [-1, 1] over its
+        # range.  num_privileged_obs is then the layout's privileged head (the quadruped's clean
+        # frame, 12 + 3 A; the humanoid's 14 + 3 A) + the tail + the scan's points.  False: off.
+        privileged_parameters = False
         num_actions = 12
         env_spacing = 3.0          # plane grid spacing [m]
         send_timeouts = True       # extras["time_outs"] for value bootstrapping

@@ -100,6 +100,25 @@ class GO2TerrainRobustCfg(GO2TerrainCfg):
         randomize_action_delay = True
 
 
+class GO2RobustAsymCfg(GO2RobustHistoryCfg):
+    """go2_robust_asym: go2_robust_history with an asymmetric critic.  The actor keeps
+    its 240 noisy inputs; the critic reads the privileged row: one clean frame (48), the shape
+    friction and added base mass (2) and the randomised actuator rows (3 x 12 + 1 = 37), 87 in all."""
+
+    class env(GO2RobustHistoryCfg.env):
+        privileged_parameters = True
+        num_privileged_obs = 87
+
+
+class GO2TerrainRobustAsymCfg(GO2TerrainRobustCfg):
+    """go2_terrain_robust_asym: go2_terrain_robust with the asymmetric critic: the 427-input actor,
+    and a critic on the clean frame, the parameter tail and the clean scan (87 + 187 = 274)."""
+
+    class env(GO2TerrainRobustCfg.env):
+        privileged_parameters = True
+        num_privileged_obs = 274
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -127,3 +146,13 @@ class GO2RobustHistoryCfgPPO(GO2RobustCfgPPO):
 class GO2TerrainRobustCfgPPO(GO2TerrainCfgPPO):
     class runner(GO2TerrainCfgPPO.runner):
         experiment_name = "go2_terrain_robust"
+
+
+class GO2RobustAsymCfgPPO(GO2RobustHistoryCfgPPO):
+    class runner(GO2RobustHistoryCfgPPO.runner):
+        experiment_name = "go2_robust_asym"
+
+
+class GO2TerrainRobustAsymCfgPPO(GO2TerrainRobustCfgPPO):
+    class runner(GO2TerrainRobustCfgPPO.runner):
+        experiment_name = "go2_terrain_robust_asym"

@@ -121,6 +121,17 @@ class ObsHistory(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("frames", C.c_int32), ("history", C.c_void_p), ("fill", C.c_void_p)]
 
 
+class PrivParams(C.Structure):
+    """lgs_priv_params: the randomised parameters as a tail of the privileged row (DESIGN 3.17);
+    {offset, scale} per group, entry = (value - offset) * scale."""
+    _fields_ = [("enabled", C.c_int32),
+                ("friction", C.c_float * 2), ("added_mass", C.c_float * 2), ("kp", C.c_float * 2),
+                ("kd", C.c_float * 2), ("strength", C.c_float * 2), ("delay", C.c_float * 2)]
+
+
+PRIV_GROUPS = ("friction", "added_mass", "kp", "kd", "strength", "delay")  # the tail's order
+
+
 class TaskParams(C.Structure):
     _fields_ = [
         ("obs_layout", C.c_int32), ("num_obs", C.c_int32), ("num_privileged_obs", C.c_int32),

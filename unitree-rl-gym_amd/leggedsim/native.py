@@ -85,6 +85,9 @@ def load():
     if hasattr(lib, "lgs_set_observation_history"):  # (absent only from pre-round-13 builds used in A/B timing)
         lib.lgs_set_observation_history.argtypes = [vp, C.POINTER(cabi.ObsHistory)]
         lib.lgs_set_observation_history.restype = C.c_int
+    if hasattr(lib, "lgs_set_privileged_parameters"):  # (absent only from pre-round-19 builds used in A/B timing)
+        lib.lgs_set_privileged_parameters.argtypes = [vp, C.POINTER(cabi.PrivParams)]
+        lib.lgs_set_privileged_parameters.restype = C.c_int
     if hasattr(lib, "lgs_get_contact_stats"):  # (absent only from pre-round-4 builds used in A/B timing)
         lib.lgs_get_contact_stats.argtypes = [vp, vp, C.c_int32]
         lib.lgs_get_contact_stats.restype = C.c_int
@@ -127,7 +130,7 @@ EXPORTED_SYMBOLS = [
     "lgs_step_deferred", "lgs_step_extras", "lgs_get_push_state",
     "lgs_set_self_collision", "lgs_get_body_name", "lgs_get_dof_name", "lgs_find_body", "lgs_find_dof",
     "lgs_get_contact_stats", "lgs_get_instantiation", "lgs_get_factor_chain", "lgs_set_height_observations",
-    "lgs_set_actuator_randomization", "lgs_set_observation_history",
+    "lgs_set_actuator_randomization", "lgs_set_observation_history", "lgs_set_privileged_parameters",
 ]
 
 
@@ -198,6 +201,12 @@ class Sim:
         self._ohist, self._ohist_buffers = desc, tuple(buffers)
         check(self.lib, self.lib.lgs_set_observation_history(self.handle, C.byref(desc)),
               "lgs_set_observation_history")
+
+    def set_privileged_parameters(self, desc):
+        """The randomised parameters as a tail of the privileged row (a cabi.PrivParams)."""
+        self._priv = desc
+        check(self.lib, self.lib.lgs_set_privileged_parameters(self.handle, C.byref(desc)),
+              "lgs_set_privileged_parameters")
 
     def bind(self, root, dofs, cforce, rbs):
         for t in (root, dofs, cforce, rbs):

@@ -205,7 +205,8 @@ def check_scan_observations(cfg, obs_layout, A):
         raise ValueError(f"terrain.scan_in_observations: env.num_observations must be {head} + {P} scan points = "
                          f"{head + P}, not {cfg.env.num_observations}")
     priv = cfg.env.num_privileged_obs
-    if priv and head_priv and priv != head_priv + P:
+    # (with env.privileged_parameters the privileged row's width is priv_params' to check)
+    if priv and head_priv and not bool(getattr(cfg.env, "privileged_parameters", False)) and priv != head_priv + P:
         raise ValueError(f"terrain.scan_in_observations: env.num_privileged_obs must be {head_priv} + {P} scan points "
                          f"= {head_priv + P}, not {priv}")
     return P
@@ -263,6 +264,57 @@ def actuator_rand_params(env) -> cabi.ActuatorRand:
     R.enabled = int(any(bool(getattr(dr, s, False)) for s in
                         ("randomize_kp", "randomize_kd", "randomize_motor_strength", "randomize_action_delay")))
     R.resample_on_reset = int(bool(R.enabled and getattr(dr, "actuator_resample_on_reset", True)))
+    return R
+
+
+def priv_params(env) -> cabi.PrivParams:
+    """lgs_priv_params of an env's cfg.env.privileged_parameters: the randomised
+    parameters as a tail of the privileged row.  A group with range [lo, hi] passes
+    offset = (lo + hi) / 2 and scale = 2 / (hi - lo) (1 when hi == lo), computed in double: a
+    randomised parameter lands in [-1, 1], a fixed one at 0.  Ranges: friction_range with
+    randomize_friction, else the terrain's static friction; added_mass_range with
+    randomize_base_mass, else [0, 0]; the actuator groups the ranges actuator_rand_params resolves.
+    The friction and mass entries are always there and the actuator entries follow the actuator
+    switches alone, so the width does not move with randomize_friction, push_robots or add_noise
+    (a checkpoint's critic still loads in play.py).  `num_tail`, `num_head` and `num_priv` (not
+    fields of the C struct): the tail's, the head's and the whole row's width.  Refused: the
+    handstand layout, a head + tail above cabi.MAX_OBS, and an env.num_privileged_obs other than the
+    row's width."""
+    R = cabi.PrivParams()
+    R.num_tail = R.num_head = R.num_priv = 0
+    cfg = env.cfg
+    if not bool(getattr(cfg.env, "privileged_parameters", False)):
+        return R
+    A = env.num_actions
+    if env.obs_layout == cabi.OBS_QUADRUPED:
+        head = 12 + 3 * A
+    elif env.obs_layout == cabi.OBS_HUMANOID:
+        head = 14 + 3 * A
+    else:
+        raise ValueError("env.privileged_parameters needs the quadruped or the humanoid observation layout (the "
+                         "handstand task's privileged row is its noisy frame)")
+    act = actuator_rand_params(env)
+    Wp = 2 + (3 * A + 1 if act.enabled else 0)
+    if head + Wp > cabi.MAX_OBS:
+        raise ValueError(f"env.privileged_parameters: the privileged head ({head}) + the parameter tail ({Wp}) = "
+                         f"{head + Wp} exceed the {cabi.MAX_OBS} entries the step's observation stage holds")
+    S = check_scan_observations(cfg, env.obs_layout, A)
+    if cfg.env.num_privileged_obs != head + Wp + S:
+        raise ValueError(f"env.privileged_parameters: env.num_privileged_obs must be {head} + {Wp} parameters + "
+                         f"{S} scan points = {head + Wp + S}, not {cfg.env.num_privileged_obs}")
+    dr = cfg.domain_rand
+    fr = list(dr.friction_range) if bool(dr.randomize_friction) else [cfg.terrain.static_friction] * 2
+    mr = list(dr.added_mass_range) if bool(dr.randomize_base_mass) else [0.0, 0.0]
+    ranges = {"friction": fr, "added_mass": mr, "kp": list(act.kp_range), "kd": list(act.kd_range),
+              "strength": list(act.strength_range), "delay": list(act.delay_range)}
+    for name in cabi.PRIV_GROUPS:
+        r = ranges[name]
+        lo, hi = (float(r[0]), float(r[1])) if len(r) == 2 else (np.nan, np.nan)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"env.privileged_parameters: the {name} range must be finite [lo, hi] with lo <= hi, "
+                             f"not {r!r}")
+        getattr(R, name)[:] = ((lo + hi) / 2.0, 2.0 / (hi - lo) if hi > lo else 1.0)
+    R.enabled, R.num_tail, R.num_head, R.num_priv = 1, Wp, head, head + Wp + S
     return R
 
 

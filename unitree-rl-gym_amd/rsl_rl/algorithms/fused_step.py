@@ -111,7 +111,7 @@ class FusedPPOStep:
         M, dev, bf = self.M, self.dev, torch.bfloat16
         L = len(self.lins[0])
         self.L = L
-        self.k0p = [mm._pad_k0(ls[0].in_features) for ls in self.lins]
+        self.k0p = mm._pad_k0_nets([ls[0].in_features for ls in self.lins])
         # row-major activations of exactly the layer's width (rows of 512 / 256 / 128 features
         # start on 128-byte lines); the weight gradients read them through LDS-transposed MFMA
         # operands (PARTIAL_TN: no transposed copy is ever written) and form the bias gradient

@@ -209,6 +209,18 @@ def _pad_k0(n):
     return _ceil8(n) if n <= 256 else (n + 63) // 64 * 64
 
 
+def _pad_k0_nets(widths):
+    """The padded first-layer widths of the nets of one fused step (actor, critic).  Nets of one
+    width keep _pad_k0's.  Where the widths differ (an asymmetric critic), a width
+    whose padding to 8 is no multiple of 16 pads to 16 instead (87 -> 96, not 88): pmlp_mlp_forward
+    takes multiples of 16 and one flag selects it for both nets, so the narrower padding would take
+    the other net off the one-launch forward as well.  The zero columns add exact zeros."""
+    pads = [_pad_k0(n) for n in widths]
+    if len(set(widths)) > 1:
+        pads = [(k + 15) // 16 * 16 for k in pads]  # (above 256 a multiple of 64 already)
+    return pads
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
