@@ -1,7 +1,8 @@
 """fp64 references, input builders and comparison functions for the scalar half of the PPO
-update in csrc/ppo_mlp.hip: the loss kernels (pmlp_ppo_loss_fwd / _bwd / _step / _step_f32, the
-loss epilogue of pmlp_mlp_forward_ppo_loss, the folded finish of pmlp_reduce_slabs_step), the
-GAE kernels, the Adam kernels and the three copies of the KL learning-rate rule.  Plain torch /
+update: the loss kernels on the core of csrc/ppo_loss.h (pmlp_ppo_loss_fwd / _bwd / _step /
+_step_f32 in csrc/ppo_loss.hip; in csrc/ppo_mlp.hip the loss epilogue of pmlp_mlp_forward_ppo_loss
+and the folded finish of pmlp_reduce_slabs_step), and in csrc/ppo_mlp.hip the GAE kernels, the
+Adam kernels and the three callers of the KL learning-rate rule.  Plain torch /
 numpy on the CPU; tests/test_ppo_ref_host.py tests these checks themselves (a float32 CPU
 evaluation passes, deliberately wrong outputs are rejected) and tests/test_gpu_ppo_reference.py
 applies them to the kernels.
@@ -617,7 +618,7 @@ FWD_LOSS_M = 18432 + 37
 
 
 def loss_arm(A, Ap):
-    """The arm loss_step_launch (csrc/ppo_mlp.hip) takes."""
+    """The arm loss_step_launch (csrc/ppo_loss.hip) takes."""
     if A % 4 == 0 and A <= 16 and Ap <= 16 and Ap % 4 == 0:
         return "quad"
     if A <= 16 and Ap % 8 == 0:

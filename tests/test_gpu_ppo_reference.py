@@ -1,5 +1,6 @@
-"""The scalar half of the PPO update in csrc/ppo_mlp.hip -- the loss kernels, the GAE kernels, the
-Adam kernels and the three copies of the KL learning-rate rule -- against the fp64 references
+"""The scalar half of the PPO update -- the loss kernels (csrc/ppo_loss.hip and the loss epilogue
+in csrc/ppo_mlp.hip, all on the one core of csrc/ppo_loss.h), the GAE kernels, the Adam kernels
+(csrc/ppo_mlp.hip) and the three callers of the KL learning-rate rule -- against the fp64 references
 of tests/ppo_ref.py, at every arm of the host's selection, with the bounds derived there (never
 fitted to what a kernel returns).  tests/test_ppo_ref_host.py applies the same comparison
 functions to deliberately wrong outputs and asserts the input conditions of every case below.

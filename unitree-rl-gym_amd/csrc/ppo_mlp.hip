@@ -1,4 +1,8 @@
-// ppo_mlp.hip — bf16 MFMA kernels for the actor-critic MLPs (include/ppo_mlp.h).
+// ppo_mlp.hip — bf16 MFMA kernels for the actor-critic MLPs (include/ppo_mlp.h), the fused
+// forward, the slab reduce, Adam, GAE and the rollout's acting side.  The PPO loss is
+// ppo_loss.h (the formulas, and loss_quad_rows for the fused forward's LOSS epilogue) and
+// ppo_loss.hip (its own kernels and entry points); pmlp_last_error's text is defined here
+// (pmlp_error.h).
 //
 // Every GEMM of an MLP layer's forward and backward is written as
 //     C[M,N] = A[M,K] . B[N,K]^T          (A, B bf16, k contiguous)
@@ -27,26 +31,23 @@
 #include <string>
 
 #include "../../include/ppo_mlp.h"
+#include "pmlp_error.h"
 #include "pmlp_noise.h"
+#include "ppo_loss.h"  // (and the bf16 types)
 
-typedef __bf16 bf16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short shortx4 __attribute__((ext_vector_type(4)));
 typedef short shortx8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) shortx4 lds_shortx4;
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
+// the text behind pmlp_last_error, also for the entry points of ppo_loss.hip (pmlp_error.h)
 static thread_local std::string g_err;
-static int fail(int code, const std::string& m) {
+int pmlp_host::fail(int code, const std::string& m) {
     g_err = m;
     return code;
 }
-#define PMLP_CHECK_LAUNCH(what)                                                                       \
-    do {                                                                                              \
-        hipError_t _e = hipGetLastError();                                                            \
-        if (_e != hipSuccess) return fail(-2, std::string(what) + ": " + hipGetErrorString(_e));      \
-    } while (0)
+using pmlp_host::fail;
+using pmlp_host::loss_args;
 
 // LDS stages of the GEMM main loop (2: one barrier per k-tile)
 // diagnostic builds (never shipped): PMLP_DIAG_NOSTORE skips the GEMM's global result
@@ -840,8 +841,8 @@ struct RedJobs {
 // G = J.groups threads per element quad (slabs g, g+G, ...), summed through LDS in group
 // order: its serial chain of dependent adds is G times shorter.
 // RedStep (pmlp_reduce_slabs_step): one more workgroup finishes the PPO loss (the
-// per-block partials of k_ppo_loss_step*: stats and the std gradient, what
-// k_ppo_loss_step_final computed, same summation order), and with norm set every
+// per-block partials of k_ppo_loss_step*, ppo_loss.hip: stats and the std gradient, what
+// k_ppo_loss_step_final computes, through the same loss_finish_quantity), and with norm set every
 // workgroup writes the sum of squares of the gradient elements it produced (the last one:
 // of the std gradient) and the loss one does k_opt_prepare's step / loss / LR bookkeeping
 // -- one launch instead of three (world size 1: nothing is all-reduced in between).
@@ -860,26 +861,13 @@ struct RedStep {
     int adaptive;
 };
 
-__device__ __forceinline__ float red_block_sum(float v, float* sh) {  // 256 threads
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 __device__ void reduce_step_finish(const RedStep& r) {
     __shared__ float q_out[64];
     __shared__ float sh[4];
     const int W = 3 + r.A, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // one wave per quantity q (q = w, w + 4, ...): k_ppo_loss_step_final's order exactly
+    // one wave per quantity q (q = w, w + 4, ...), summed as k_ppo_loss_step_final sums it
     for (int q = w; q < W; q += 4) {
-        float x = 0.f;
-#pragma unroll 8
-        for (int b = lane; b < r.lblocks; b += 64) x += r.lpartial[(size_t)b * W + q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+        const float x = loss_finish_quantity(r.lpartial, r.lblocks, W, q, lane);
         if (lane == 0) q_out[q] = x;
     }
     __syncthreads();
@@ -895,13 +883,9 @@ __device__ void reduce_step_finish(const RedStep& r) {
             sq = d * d;
         }
     }
-    if (threadIdx.x == 0) {
-        float ent = 0.f;
-        for (int k = 0; k < r.A; ++k) ent += 0.5f + 0.91893853320467274f + logf(r.stdv[k]);  // log(sqrt(2 pi))
-        r.stats[3] = ent;
-    }
+    if (threadIdx.x == 0) r.stats[3] = entropy_sum(r.stdv, r.A);
     if (!r.norm) return;  // (block-uniform)
-    sq = red_block_sum(sq, sh);
+    sq = block_sum(sq, sh);
     if (threadIdx.x == 0) {
         r.norm[blockIdx.x] = sq;
         // k_opt_prepare's block-0 bookkeeping at scale 1 (the stats of this launch)
@@ -911,13 +895,7 @@ __device__ void reduce_step_finish(const RedStep& r) {
             r.acc[0] += s1;
             r.acc[1] += s0;
         }
-        if (r.adaptive) {
-            const float kl = q_out[2] * (1.f / (float)r.M);
-            float l = r.lr[0];
-            if (kl > r.desired_kl * 2.f) l = fmaxf(l / 1.5f, 1e-5f);
-            else if (kl < r.desired_kl / 2.f && kl > 0.f) l = fminf(l * 1.5f, 1e-2f);
-            r.lr[0] = l;
-        }
+        if (r.adaptive) r.lr[0] = kl_lr_rule(q_out[2] * (1.f / (float)r.M), r.lr[0], r.desired_kl);
     }
 }
 
@@ -983,7 +961,7 @@ __global__ __launch_bounds__(256) void k_reduce_jobs(RedJobs jobs, RedStep rs) {
         }
     }
     if (!rs.norm) return;  // (block-uniform)
-    sq = red_block_sum(sq, sh);
+    sq = block_sum(sq, sh);
     if (threadIdx.x == 0) rs.norm[blockIdx.x] = sq;
 }
 
@@ -1016,571 +994,6 @@ __global__ __launch_bounds__(256) void k_rowsum_jobs(SumJobs jobs) {
     if (tid == 0) J.out[r] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-
-// ---------------------------------------------------------------- PPO loss --
-// rsl_rl v1.0.2 PPO.update loss for a diagonal Gaussian policy, one row per
-// thread, forward and backward fused (see ppo.py _minibatch_step for the torch
-// statement it replaces).  Reductions: per-block partials, then one block sums
-// them in a fixed order (deterministic).
-#define PMLP_LOSS_THREADS 256
-struct LossArgs {
-    const float *mu, *stdv, *value, *actions, *old_logp, *old_mu, *old_sigma, *adv, *ret, *target;
-    const int64_t* rows;  // optional: rollout inputs (actions .. target) are read at row rows[i]
-    int M, A, clipped_value;
-    float clip, vcoef, ecoef;
-    __device__ size_t src(int i) const { return rows ? (size_t)rows[i] : (size_t)i; }
-};
-
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__global__ __launch_bounds__(PMLP_LOSS_THREADS) void k_ppo_loss_fwd(LossArgs a, float* __restrict__ partial) {
-    __shared__ float sh[4];
-    const int i = blockIdx.x * PMLP_LOSS_THREADS + threadIdx.x;
-    float surr = 0.f, vl = 0.f, kl = 0.f;
-    if (i < a.M) {
-        const size_t si = a.src(i);
-        float logp = 0.f;
-        for (int k = 0; k < a.A; ++k) {
-            const float sg = a.stdv[k], mu = a.mu[(size_t)i * a.A + k];
-            const float d = a.actions[si * a.A + k] - mu;
-            logp += -(d * d) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-            const float os = a.old_sigma[si * a.A + k], om = a.old_mu[si * a.A + k] - mu;
-            kl += logf(sg / os + 1.0e-5f) + (os * os + om * om) / (2.f * sg * sg) - 0.5f;
-        }
-        const float ratio = expf(logp - a.old_logp[si]);
-        const float adv = a.adv[si];
-        const float s1 = -adv * ratio, s2 = -adv * fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip);
-        surr = fmaxf(s1, s2);
-        const float v = a.value[i], r = a.ret[si];
-        if (a.clipped_value) {
-            const float t = a.target[si];
-            const float vc = t + fminf(fmaxf(v - t, -a.clip), a.clip);
-            vl = fmaxf((v - r) * (v - r), (vc - r) * (vc - r));
-        } else {
-            vl = (r - v) * (r - v);
-        }
-    }
-    surr = block_sum(surr, sh);
-    vl = block_sum(vl, sh);
-    kl = block_sum(kl, sh);
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x * 4 + 0] = surr;
-        partial[blockIdx.x * 4 + 1] = vl;
-        partial[blockIdx.x * 4 + 2] = kl;
-    }
-}
-
-// loss[0]; stats = [surrogate_loss, value_loss, kl_mean, entropy_mean]
-__global__ __launch_bounds__(PMLP_LOSS_THREADS) void k_ppo_loss_final(LossArgs a, const float* __restrict__ partial,
-                                                                      int nblocks, float* __restrict__ loss,
-                                                                      float* __restrict__ stats) {
-    __shared__ float sh[4];
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int b = threadIdx.x; b < nblocks; b += PMLP_LOSS_THREADS)
-        for (int k = 0; k < 3; ++k) s[k] += partial[b * 4 + k];
-    for (int k = 0; k < 3; ++k) s[k] = block_sum(s[k], sh);
-    if (threadIdx.x == 0) {
-        float ent = 0.f;
-        for (int k = 0; k < a.A; ++k) ent += 0.5f + kHalfLog2Pi + logf(a.stdv[k]);
-        const float inv = 1.f / (float)a.M;
-        const float surr = s[0] * inv, vl = s[1] * inv;
-        loss[0] = surr + a.vcoef * vl - a.ecoef * ent;
-        stats[0] = surr;
-        stats[1] = vl;
-        stats[2] = s[2] * inv;
-        stats[3] = ent;
-    }
-}
-
-// torch.maximum backward: the larger input takes the gradient, ties split it
-__device__ __forceinline__ void max_weights(float x, float y, float& wx, float& wy) {
-    wx = x > y ? 1.f : (x == y ? 0.5f : 0.f);
-    wy = y > x ? 1.f : (x == y ? 0.5f : 0.f);
-}
-
-__global__ __launch_bounds__(PMLP_LOSS_THREADS) void k_ppo_loss_bwd(LossArgs a, const float* __restrict__ gout,
-                                                                    float* __restrict__ dmu, float* __restrict__ dvalue,
-                                                                    float* __restrict__ partial_std) {
-    __shared__ float sh[4];
-    const int i = blockIdx.x * PMLP_LOSS_THREADS + threadIdx.x;
-    const float g = gout[0];
-    const float gs = g / (float)a.M, gv = g * a.vcoef / (float)a.M;
-    float dlogp = 0.f;
-    const size_t si = i < a.M ? a.src(i) : 0;
-    if (i < a.M) {
-        float logp = 0.f;
-        for (int k = 0; k < a.A; ++k) {
-            const float sg = a.stdv[k];
-            const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-            logp += -(d * d) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-        }
-        const float ratio = expf(logp - a.old_logp[si]);
-        const float adv = a.adv[si];
-        const float lo = 1.f - a.clip, hi = 1.f + a.clip;
-        const float s1 = -adv * ratio, s2 = -adv * fminf(fmaxf(ratio, lo), hi);
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        const float dclamp = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-        dlogp = gs * (-adv) * (w1 + w2 * dclamp) * ratio;
-        for (int k = 0; k < a.A; ++k) {
-            const float sg = a.stdv[k];
-            const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-            dmu[(size_t)i * a.A + k] = dlogp * d / (sg * sg);
-        }
-        const float v = a.value[i], r = a.ret[si];
-        float dv;
-        if (a.clipped_value) {
-            const float t = a.target[si];
-            const float vc = t + fminf(fmaxf(v - t, -a.clip), a.clip);
-            float u1, u2;
-            max_weights((v - r) * (v - r), (vc - r) * (vc - r), u1, u2);
-            const float dcv = (v - t >= -a.clip && v - t <= a.clip) ? 1.f : 0.f;
-            dv = gv * (u1 * 2.f * (v - r) + u2 * 2.f * (vc - r) * dcv);
-        } else {
-            dv = gv * 2.f * (v - r);
-        }
-        dvalue[i] = dv;
-    }
-    // d logp / d sigma_k summed over the block's rows
-    for (int k = 0; k < a.A; ++k) {
-        float c = 0.f;
-        if (i < a.M) {
-            const float sg = a.stdv[k];
-            const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-            c = dlogp * (d * d / (sg * sg * sg) - 1.f / sg);
-        }
-        c = block_sum(c, sh);
-        if (threadIdx.x == 0) partial_std[(size_t)blockIdx.x * a.A + k] = c;
-    }
-}
-
-__global__ __launch_bounds__(PMLP_LOSS_THREADS) void k_ppo_loss_std(LossArgs a, const float* __restrict__ gout,
-                                                                    const float* __restrict__ partial_std, int nblocks,
-                                                                    float* __restrict__ dstd) {
-    __shared__ float sh[4];
-    for (int k = 0; k < a.A; ++k) {
-        float c = 0.f;
-        for (int b = threadIdx.x; b < nblocks; b += PMLP_LOSS_THREADS) c += partial_std[(size_t)b * a.A + k];
-        c = block_sum(c, sh);
-        if (threadIdx.x == 0) dstd[k] = c - a.ecoef * gout[0] / a.stdv[k];  // + entropy term
-    }
-}
-
-// Fused PPO loss forward + backward for the optimizer step (the gradient of the
-// loss itself, gout = 1): one wave per 64 rows, writing the output gradients straight
-// into the MLP backward's bf16 operands (row-major and transposed, padded columns
-// zero) and per-wave partials of [surrogate, value loss, kl, d/dstd_k (k < A)].
-struct LossStepOut {
-    float* partial;
-    bf16 *dmu_b, *dmu_t, *dv_b, *dv_t;
-    int Ap, Vp;  // padded widths of the actor / critic output gradients (0: no bf16 output)
-    float *dmu_f, *dv_f;  // optional fp32 output gradients [M, A] and [M] (the recurrent heads)
-};
-__global__ __launch_bounds__(64) void k_ppo_loss_step(LossArgs a, LossStepOut o) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const int W = 3 + a.A;
-    float surr = 0.f, vl = 0.f, kl = 0.f, dlogp = 0.f;
-    const bool valid = i < a.M;
-    const size_t si = valid ? a.src(i) : 0;
-    if (valid) {
-        float logp = 0.f;
-        for (int k = 0; k < a.A; ++k) {
-            const float sg = a.stdv[k], mu = a.mu[(size_t)i * a.A + k];
-            const float d = a.actions[si * a.A + k] - mu;
-            logp += -(d * d) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-            const float os = a.old_sigma[si * a.A + k], om = a.old_mu[si * a.A + k] - mu;
-            kl += logf(sg / os + 1.0e-5f) + (os * os + om * om) / (2.f * sg * sg) - 0.5f;
-        }
-        const float ratio = expf(logp - a.old_logp[si]);
-        const float adv = a.adv[si];
-        const float lo = 1.f - a.clip, hi = 1.f + a.clip;
-        const float s1 = -adv * ratio, s2 = -adv * fminf(fmaxf(ratio, lo), hi);
-        surr = fmaxf(s1, s2);
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        const float dclamp = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-        const float gs = 1.f / (float)a.M, gv = a.vcoef / (float)a.M;
-        dlogp = gs * (-adv) * (w1 + w2 * dclamp) * ratio;
-        for (int k = 0; k < o.Ap; ++k) {
-            float g = 0.f;
-            if (k < a.A) {
-                const float sg = a.stdv[k];
-                const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-                g = dlogp * d / (sg * sg);
-            }
-            o.dmu_b[(size_t)i * o.Ap + k] = (bf16)g;
-            if (o.dmu_t) o.dmu_t[(size_t)k * a.M + i] = (bf16)g;
-        }
-        if (o.dmu_f)
-            for (int k = 0; k < a.A; ++k) {
-                const float sg = a.stdv[k];
-                const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-                o.dmu_f[(size_t)i * a.A + k] = dlogp * d / (sg * sg);
-            }
-        const float v = a.value[i], r = a.ret[si];
-        float dv;
-        if (a.clipped_value) {
-            const float t = a.target[si];
-            const float vc = t + fminf(fmaxf(v - t, -a.clip), a.clip);
-            vl = fmaxf((v - r) * (v - r), (vc - r) * (vc - r));
-            float u1, u2;
-            max_weights((v - r) * (v - r), (vc - r) * (vc - r), u1, u2);
-            const float dcv = (v - t >= -a.clip && v - t <= a.clip) ? 1.f : 0.f;
-            dv = gv * (u1 * 2.f * (v - r) + u2 * 2.f * (vc - r) * dcv);
-        } else {
-            vl = (r - v) * (r - v);
-            dv = gv * 2.f * (v - r);
-        }
-        for (int k = 0; k < o.Vp; ++k) {
-            o.dv_b[(size_t)i * o.Vp + k] = (bf16)(k == 0 ? dv : 0.f);
-            if (o.dv_t) o.dv_t[(size_t)k * a.M + i] = (bf16)(k == 0 ? dv : 0.f);
-        }
-        if (o.dv_f) o.dv_f[i] = dv;
-    }
-    auto wsum = [](float x) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        return x;
-    };
-    surr = wsum(surr);
-    vl = wsum(vl);
-    kl = wsum(kl);
-    if (threadIdx.x == 0) {
-        o.partial[(size_t)blockIdx.x * W + 0] = surr;
-        o.partial[(size_t)blockIdx.x * W + 1] = vl;
-        o.partial[(size_t)blockIdx.x * W + 2] = kl;
-    }
-    for (int k = 0; k < a.A; ++k) {
-        float c = 0.f;
-        if (valid) {
-            const float sg = a.stdv[k];
-            const float d = a.actions[si * a.A + k] - a.mu[(size_t)i * a.A + k];
-            c = dlogp * (d * d / (sg * sg * sg) - 1.f / sg);
-        }
-        c = wsum(c);
-        if (threadIdx.x == 0) o.partial[(size_t)blockIdx.x * W + 3 + k] = c;
-    }
-}
-
-// The same step with the row's A <= AM action entries held in registers (loaded once,
-// gathered rows read as one contiguous record) and the per-action constants of sigma
-// (1/(2s^2), 1/s^2, 1/s^3, 1/s, log s) computed once per block: the generic kernel above
-// re-reads actions/mu in each of its three loops and takes 12 logf(sigma) per row.
-template <int AM>
-__global__ __launch_bounds__(64) void k_ppo_loss_step_reg(LossArgs a, LossStepOut o) {
-    __shared__ float c_h[AM], c_i2[AM], c_i3[AM], c_i1[AM], c_lg[AM], c_sg[AM];
-    const int A = a.A, W = 3 + A;
-    if (threadIdx.x < A) {
-        const float sg = a.stdv[threadIdx.x];
-        c_sg[threadIdx.x] = sg;
-        c_h[threadIdx.x] = 1.f / (2.f * sg * sg);
-        c_i2[threadIdx.x] = 1.f / (sg * sg);
-        c_i3[threadIdx.x] = 1.f / (sg * sg * sg);
-        c_i1[threadIdx.x] = 1.f / sg;
-        c_lg[threadIdx.x] = logf(sg);
-    }
-    __syncthreads();
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    const bool valid = i < a.M;
-    const size_t si = valid ? a.src(i) : 0;
-    float d[AM];
-    float surr = 0.f, vl = 0.f, kl = 0.f, dlogp = 0.f;
-    if (valid) {
-        // the row's records: 16-byte loads when A is a multiple of 4 (every record then
-        // starts on 16 bytes), else one float per entry
-        float rmu[AM], ract[AM], ros[AM], rom[AM];
-        if ((A & 3) == 0) {
-#pragma unroll
-            for (int k = 0; k < AM; k += 4) {
-                if (k < A) {
-                    const float4 m4 = *(const float4*)(a.mu + (size_t)i * A + k);
-                    const float4 a4 = *(const float4*)(a.actions + si * A + k);
-                    const float4 s4 = *(const float4*)(a.old_sigma + si * A + k);
-                    const float4 o4 = *(const float4*)(a.old_mu + si * A + k);
-                    rmu[k] = m4.x; rmu[k + 1] = m4.y; rmu[k + 2] = m4.z; rmu[k + 3] = m4.w;
-                    ract[k] = a4.x; ract[k + 1] = a4.y; ract[k + 2] = a4.z; ract[k + 3] = a4.w;
-                    ros[k] = s4.x; ros[k + 1] = s4.y; ros[k + 2] = s4.z; ros[k + 3] = s4.w;
-                    rom[k] = o4.x; rom[k + 1] = o4.y; rom[k + 2] = o4.z; rom[k + 3] = o4.w;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < AM; ++k)
-                if (k < A) {
-                    rmu[k] = a.mu[(size_t)i * A + k];
-                    ract[k] = a.actions[si * A + k];
-                    ros[k] = a.old_sigma[si * A + k];
-                    rom[k] = a.old_mu[si * A + k];
-                }
-        }
-        float logp = 0.f;
-#pragma unroll
-        for (int k = 0; k < AM; ++k) {
-            if (k < A) {
-                const float mu = rmu[k];
-                d[k] = ract[k] - mu;
-                logp += -(d[k] * d[k]) * c_h[k] - c_lg[k] - kHalfLog2Pi;
-                const float os = ros[k], om = rom[k] - mu;
-                kl += logf(c_sg[k] / os + 1.0e-5f) + (os * os + om * om) * c_h[k] - 0.5f;
-            } else {
-                d[k] = 0.f;
-            }
-        }
-        const float ratio = expf(logp - a.old_logp[si]);
-        const float adv = a.adv[si];
-        const float lo = 1.f - a.clip, hi = 1.f + a.clip;
-        const float s1 = -adv * ratio, s2 = -adv * fminf(fmaxf(ratio, lo), hi);
-        surr = fmaxf(s1, s2);
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        const float dclamp = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-        dlogp = (1.f / (float)a.M) * (-adv) * (w1 + w2 * dclamp) * ratio;
-        for (int k = 0; k < o.Ap; k += 8) {  // 16-byte chunks of the padded dmu row
-            bf16x8 g;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float gv = 0.f;
-#pragma unroll
-                for (int kk = 0; kk < AM; ++kk)
-                    if (kk == k + u && kk < A) gv = dlogp * d[kk] * c_i2[kk];
-                g[u] = (bf16)gv;
-                if (o.dmu_t) o.dmu_t[(size_t)(k + u) * a.M + i] = (bf16)gv;
-            }
-            *(bf16x8*)(o.dmu_b + (size_t)i * o.Ap + k) = g;
-        }
-        if (o.dmu_f) {
-#pragma unroll
-            for (int kk = 0; kk < AM; ++kk)
-                if (kk < A) o.dmu_f[(size_t)i * A + kk] = dlogp * d[kk] * c_i2[kk];
-        }
-        const float v = a.value[i], r = a.ret[si];
-        float dv;
-        const float gvc = a.vcoef / (float)a.M;
-        if (a.clipped_value) {
-            const float t = a.target[si];
-            const float vc = t + fminf(fmaxf(v - t, -a.clip), a.clip);
-            vl = fmaxf((v - r) * (v - r), (vc - r) * (vc - r));
-            float u1, u2;
-            max_weights((v - r) * (v - r), (vc - r) * (vc - r), u1, u2);
-            const float dcv = (v - t >= -a.clip && v - t <= a.clip) ? 1.f : 0.f;
-            dv = gvc * (u1 * 2.f * (v - r) + u2 * 2.f * (vc - r) * dcv);
-        } else {
-            vl = (r - v) * (r - v);
-            dv = gvc * 2.f * (v - r);
-        }
-        for (int k = 0; k < o.Vp; ++k) {
-            o.dv_b[(size_t)i * o.Vp + k] = (bf16)(k == 0 ? dv : 0.f);
-            if (o.dv_t) o.dv_t[(size_t)k * a.M + i] = (bf16)(k == 0 ? dv : 0.f);
-        }
-        if (o.dv_f) o.dv_f[i] = dv;
-    } else {
-#pragma unroll
-        for (int k = 0; k < AM; ++k) d[k] = 0.f;
-    }
-    auto wsum = [](float x) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-        return x;
-    };
-    surr = wsum(surr);
-    vl = wsum(vl);
-    kl = wsum(kl);
-    if (threadIdx.x == 0) {
-        o.partial[(size_t)blockIdx.x * W + 0] = surr;
-        o.partial[(size_t)blockIdx.x * W + 1] = vl;
-        o.partial[(size_t)blockIdx.x * W + 2] = kl;
-    }
-#pragma unroll
-    for (int k = 0; k < AM; ++k) {
-        if (k < A) {
-            float c = valid ? dlogp * (d[k] * d[k] * c_i3[k] - c_i1[k]) : 0.f;
-            c = wsum(c);
-            if (threadIdx.x == 0) o.partial[(size_t)blockIdx.x * W + 3 + k] = c;
-        }
-    }
-}
-
-// The same step with four lanes per row (lane q of a quad owns action entries 4q..4q+3: one
-// 16-byte load per record instead of A/4 serial ones) in 256-thread blocks of 64 rows, so
-// the 24,576-row mini-batch is 1,536 waves instead of 384 and each lane has a quarter of
-// the gathers in flight.  Quad sums combine a row's logp / KL; the block's partials are
-// summed per wave (rows in xor order), then over the 4 waves in order (deterministic; the
-// same partials layout as k_ppo_loss_step_reg: one record of 3 + A per 64 rows).
-// Needs A % 4 == 0, A <= 16, Ap <= 16 and Ap % 4 == 0.
-// The quad-lane loss on rows i0 .. i0 + 16 NWV - 1: four lanes per row (each owning 4 actions),
-// 16 rows per wave, NWV waves (threads past 64 NWV join the barriers only); the per-wave sums
-// are added in a fixed order into partial row `part`.  sh: LDS scratch of >= 96 + 19 NWV floats.
-// k_ppo_loss_step_q (NWV = 4, 64 rows per workgroup) and the update forward's epilogue
-// (k_mlp_fwd<96, .., LOSS>: NWV = 6, the workgroup's 96 rows; the WIDER form's 64 rows: NWV = 4)
-// run it.
-template <int NWV>
-__device__ __forceinline__ void loss_quad_rows(const LossArgs& a, const LossStepOut& o, int i0, int part, float* sh) {
-    float* const c_h = sh;
-    float* const c_i2 = sh + 16;
-    float* const c_i3 = sh + 32;
-    float* const c_i1 = sh + 48;
-    float* const c_lg = sh + 64;
-    float* const c_sg = sh + 80;
-    float(*const wpart)[3 + 16] = (float(*)[3 + 16])(sh + 96);
-    const int A = a.A, W = 3 + A, tid = threadIdx.x, q = tid & 3, k0 = 4 * q;
-    if (tid < A) {
-        const float sg = a.stdv[tid];
-        c_sg[tid] = sg;
-        c_h[tid] = 1.f / (2.f * sg * sg);
-        c_i2[tid] = 1.f / (sg * sg);
-        c_i3[tid] = 1.f / (sg * sg * sg);
-        c_i1[tid] = 1.f / sg;
-        c_lg[tid] = logf(sg);
-    }
-    __syncthreads();
-    const int i = i0 + (tid >> 2);
-    const bool valid = tid < 64 * NWV && i < a.M;
-    const bool own = k0 < A;  // quad-uniform per lane, same for every row
-    const size_t si = valid ? a.src(i) : 0;
-    float d[4] = {0.f, 0.f, 0.f, 0.f};
-    float surr = 0.f, vl = 0.f, kl = 0.f, dlogp = 0.f;
-    if (valid) {
-        float lp = 0.f, kp = 0.f;
-        if (own) {
-            const float4 m4 = *(const float4*)(a.mu + (size_t)i * A + k0);
-            const float4 a4 = *(const float4*)(a.actions + si * A + k0);
-            const float4 s4 = *(const float4*)(a.old_sigma + si * A + k0);
-            const float4 o4 = *(const float4*)(a.old_mu + si * A + k0);
-            const float rmu[4] = {m4.x, m4.y, m4.z, m4.w}, ract[4] = {a4.x, a4.y, a4.z, a4.w};
-            const float ros[4] = {s4.x, s4.y, s4.z, s4.w}, rom[4] = {o4.x, o4.y, o4.z, o4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + u;
-                d[u] = ract[u] - rmu[u];
-                lp += -(d[u] * d[u]) * c_h[k] - c_lg[k] - kHalfLog2Pi;
-                const float os = ros[u], om = rom[u] - rmu[u];
-                kp += logf(c_sg[k] / os + 1.0e-5f) + (os * os + om * om) * c_h[k] - 0.5f;
-            }
-        }
-        lp += __shfl_xor(lp, 1);
-        lp += __shfl_xor(lp, 2);
-        kp += __shfl_xor(kp, 1);
-        kp += __shfl_xor(kp, 2);
-        const float ratio = expf(lp - a.old_logp[si]);
-        const float adv = a.adv[si];
-        const float lo = 1.f - a.clip, hi = 1.f + a.clip;
-        const float s1 = -adv * ratio, s2 = -adv * fminf(fmaxf(ratio, lo), hi);
-        float w1, w2;
-        max_weights(s1, s2, w1, w2);
-        const float dclamp = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-        dlogp = (1.f / (float)a.M) * (-adv) * (w1 + w2 * dclamp) * ratio;
-        if (k0 < o.Ap) {
-            bf16x4 g;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) g[u] = (bf16)(own ? dlogp * d[u] * c_i2[k0 + u] : 0.f);
-            *(bf16x4*)(o.dmu_b + (size_t)i * o.Ap + k0) = g;
-            if (o.dmu_t) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) o.dmu_t[(size_t)(k0 + u) * a.M + i] = g[u];
-            }
-        }
-        const float v = a.value[i], r = a.ret[si];
-        float dv;
-        const float gvc = a.vcoef / (float)a.M;
-        float vq;
-        if (a.clipped_value) {
-            const float t = a.target[si];
-            const float vc = t + fminf(fmaxf(v - t, -a.clip), a.clip);
-            vq = fmaxf((v - r) * (v - r), (vc - r) * (vc - r));
-            float u1, u2;
-            max_weights((v - r) * (v - r), (vc - r) * (vc - r), u1, u2);
-            const float dcv = (v - t >= -a.clip && v - t <= a.clip) ? 1.f : 0.f;
-            dv = gvc * (u1 * 2.f * (v - r) + u2 * 2.f * (vc - r) * dcv);
-        } else {
-            vq = (r - v) * (r - v);
-            dv = gvc * 2.f * (v - r);
-        }
-        for (int k = q; k < o.Vp; k += 4) {
-            o.dv_b[(size_t)i * o.Vp + k] = (bf16)(k == 0 ? dv : 0.f);
-            if (o.dv_t) o.dv_t[(size_t)k * a.M + i] = (bf16)(k == 0 ? dv : 0.f);
-        }
-        if (o.dv_f && q == 0) o.dv_f[i] = dv;
-        if (o.dmu_f && own) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) o.dmu_f[(size_t)i * A + k0 + u] = dlogp * d[u] * c_i2[k0 + u];
-        }
-        if (q == 0) {  // the row's scalars counted once
-            surr = fmaxf(s1, s2);
-            vl = vq;
-            kl = kp;
-        }
-    }
-    // per wave: sums over its 16 rows (xor 4..32 keeps the quad position), then the
-    // scalars (nonzero on q == 0 only) over the quad
-    auto rsum = [](float x) {
-#pragma unroll
-        for (int off = 4; off < 64; off <<= 1) x += __shfl_xor(x, off);
-        return x;
-    };
-    surr = rsum(surr);
-    vl = rsum(vl);
-    kl = rsum(kl);
-    float c[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int k = k0 + u;
-        c[u] = rsum(valid && own ? dlogp * (d[u] * d[u] * c_i3[k] - c_i1[k]) : 0.f);
-    }
-    const int w = tid >> 6, lane = tid & 63;
-    if (lane == 0 && w < NWV) {
-        wpart[w][0] = surr;
-        wpart[w][1] = vl;
-        wpart[w][2] = kl;
-    }
-    if (lane < 4 && own && w < NWV) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) wpart[w][3 + k0 + u] = c[u];
-    }
-    __syncthreads();
-    if (tid < W) {
-        float x = (wpart[0][tid] + wpart[1][tid]) + (wpart[2][tid] + wpart[3][tid]);
-#pragma unroll
-        for (int v = 4; v < NWV; v += 2) x += wpart[v][tid] + wpart[v + 1][tid];
-        o.partial[(size_t)part * W + tid] = x;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ppo_loss_step_q(LossArgs a, LossStepOut o) {
-    __shared__ float sh[96 + 4 * 19];
-    loss_quad_rows<4>(a, o, blockIdx.x * 64, blockIdx.x, sh);
-}
-
-// stats = [surrogate_loss, value_loss, kl_mean, entropy_mean]; dstd[k] incl. the entropy term.
-// One wave per reduced quantity q (block q): the per-wave partials of k_ppo_loss_step summed
-// in a fixed order (deterministic), all quantities at once.
-__global__ __launch_bounds__(64) void k_ppo_loss_step_final(LossArgs a, const float* __restrict__ partial,
-                                                            int nblocks, float* __restrict__ stats,
-                                                            float* __restrict__ dstd) {
-    const int W = 3 + a.A, q = blockIdx.x;
-    float x = 0.f;
-#pragma unroll 8
-    for (int b = threadIdx.x; b < nblocks; b += 64) x += partial[(size_t)b * W + q];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    if (threadIdx.x == 0) {
-        if (q < 3) stats[q] = x * (1.f / (float)a.M);
-        else dstd[q - 3] = x - a.ecoef / a.stdv[q - 3];
-        if (q == 0) {
-            float ent = 0.f;
-            for (int k = 0; k < a.A; ++k) ent += 0.5f + kHalfLog2Pi + logf(a.stdv[k]);
-            stats[3] = ent;
-        }
-    }
-}
-
 // ------------------------------------------------------------ optimizer --
 // One PPO optimizer step over the FLAT parameter/gradient buffers (every
 // actor/critic parameter is a view of one fp32 buffer): clip_grad_norm_ +
@@ -1599,13 +1012,7 @@ __global__ void k_loss_bookkeeping(const float* __restrict__ stats, float* lr, f
         acc[0] += stats[1];
         acc[1] += stats[0];
     }
-    if (adaptive) {
-        const float kl = stats[2];
-        float l = lr[0];
-        if (kl > desired_kl * 2.f) l = fmaxf(l / 1.5f, 1e-5f);
-        else if (kl < desired_kl / 2.f && kl > 0.f) l = fminf(l * 1.5f, 1e-2f);
-        lr[0] = l;
-    }
+    if (adaptive) lr[0] = kl_lr_rule(stats[2], lr[0], desired_kl);
 }
 
 // partial[b] = sum of (scale*g)^2 over block b's grid-stride share; block 0 also
@@ -1634,13 +1041,7 @@ __global__ __launch_bounds__(PMLP_OPT_THREADS) void k_opt_prepare(const float* _
                 acc[0] += stats[1] * scale;
                 acc[1] += stats[0] * scale;
             }
-            if (adaptive) {  // rsl_rl v1.0.2 PPO.update: KL-adaptive learning rate
-                const float kl = stats[2] * scale;
-                float l = lr[0];
-                if (kl > desired_kl * 2.f) l = fmaxf(l / 1.5f, 1e-5f);
-                else if (kl < desired_kl / 2.f && kl > 0.f) l = fminf(l * 1.5f, 1e-2f);
-                lr[0] = l;
-            }
+            if (adaptive) lr[0] = kl_lr_rule(stats[2] * scale, lr[0], desired_kl);
         }
     }
 }
@@ -2753,58 +2154,6 @@ PMLP_API int pmlp_rowsum(int32_t njobs, const pmlp_rowsum_job* jobs, void* strea
     return 0;
 }
 
-
-static int loss_args(LossArgs& a, const float* mu, const float* stdv, const float* value, const float* actions,
-                     const float* old_logp, const float* old_mu, const float* old_sigma, const float* adv,
-                     const float* ret, const float* target, const int64_t* rows, int32_t M, int32_t A, float clip,
-                     int32_t clipped_value, float vcoef, float ecoef) {
-    if (!mu || !stdv || !value || !actions || !old_logp || !old_mu || !old_sigma || !adv || !ret ||
-        (clipped_value && !target) || M <= 0 || A <= 0)
-        return fail(-1, "pmlp_ppo_loss: null input or empty batch");
-    a = LossArgs{mu, stdv, value, actions, old_logp, old_mu, old_sigma, adv, ret, target, rows, M, A, clipped_value,
-                 clip, vcoef, ecoef};
-    return 0;
-}
-
-PMLP_API int32_t pmlp_ppo_loss_blocks(int32_t M) { return (M + PMLP_LOSS_THREADS - 1) / PMLP_LOSS_THREADS; }
-
-PMLP_API int pmlp_ppo_loss_fwd(const float* mu, const float* stdv, const float* value, const float* actions,
-                               const float* old_logp, const float* old_mu, const float* old_sigma, const float* adv,
-                               const float* ret, const float* target, const int64_t* rows, int32_t M, int32_t A,
-                               float clip, int32_t clipped_value, float vcoef, float ecoef, float* partial, float* loss,
-                               float* stats, void* stream) {
-    LossArgs a;
-    if (int e = loss_args(a, mu, stdv, value, actions, old_logp, old_mu, old_sigma, adv, ret, target, rows, M, A, clip,
-                          clipped_value, vcoef, ecoef))
-        return e;
-    if (!partial || !loss || !stats) return fail(-1, "pmlp_ppo_loss_fwd: null output");
-    const int nb = pmlp_ppo_loss_blocks(M);
-    hipLaunchKernelGGL(k_ppo_loss_fwd, dim3(nb), dim3(PMLP_LOSS_THREADS), 0, (hipStream_t)stream, a, partial);
-    hipLaunchKernelGGL(k_ppo_loss_final, dim3(1), dim3(PMLP_LOSS_THREADS), 0, (hipStream_t)stream, a, partial, nb,
-                       loss, stats);
-    PMLP_CHECK_LAUNCH("pmlp_ppo_loss_fwd");
-    return 0;
-}
-
-PMLP_API int pmlp_ppo_loss_bwd(const float* mu, const float* stdv, const float* value, const float* actions,
-                               const float* old_logp, const float* old_mu, const float* old_sigma, const float* adv,
-                               const float* ret, const float* target, const int64_t* rows, int32_t M, int32_t A,
-                               float clip, int32_t clipped_value, float vcoef, float ecoef, const float* gout,
-                               float* dmu, float* dvalue, float* partial_std, float* dstd, void* stream) {
-    LossArgs a;
-    if (int e = loss_args(a, mu, stdv, value, actions, old_logp, old_mu, old_sigma, adv, ret, target, rows, M, A, clip,
-                          clipped_value, vcoef, ecoef))
-        return e;
-    if (!gout || !dmu || !dvalue || !partial_std || !dstd) return fail(-1, "pmlp_ppo_loss_bwd: null output");
-    const int nb = pmlp_ppo_loss_blocks(M);
-    hipLaunchKernelGGL(k_ppo_loss_bwd, dim3(nb), dim3(PMLP_LOSS_THREADS), 0, (hipStream_t)stream, a, gout, dmu, dvalue,
-                       partial_std);
-    hipLaunchKernelGGL(k_ppo_loss_std, dim3(1), dim3(PMLP_LOSS_THREADS), 0, (hipStream_t)stream, a, gout,
-                       partial_std, nb, dstd);
-    PMLP_CHECK_LAUNCH("pmlp_ppo_loss_bwd");
-    return 0;
-}
-
 PMLP_API int32_t pmlp_opt_parts(void) { return PMLP_OPT_PARTS; }
 
 PMLP_API int pmlp_opt_prepare(const float* grad, int64_t n, float grad_scale, float* partial, float* step,
@@ -3168,40 +2517,6 @@ PMLP_API int pmlp_store_step(const float* rewards, const uint8_t* dones, const u
 }
 
 
-PMLP_API int32_t pmlp_ppo_loss_step_parts(int32_t M, int32_t A) { return ((M + 63) / 64) * (3 + A); }
-
-static int loss_step_launch(const LossArgs& a, const LossStepOut& o, int M, int A, int Ap, float* partial,
-                            float* stats, float* dstd, void* stream) {
-    const int nb = (M + 63) / 64;
-    if (A % 4 == 0 && A <= 16 && Ap <= 16 && Ap % 4 == 0)
-        hipLaunchKernelGGL(k_ppo_loss_step_q, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, o);
-    else if (A <= 16 && Ap % 8 == 0)
-        hipLaunchKernelGGL(k_ppo_loss_step_reg<16>, dim3(nb), dim3(64), 0, (hipStream_t)stream, a, o);
-    else
-        hipLaunchKernelGGL(k_ppo_loss_step, dim3(nb), dim3(64), 0, (hipStream_t)stream, a, o);
-    if (stats)  // (stats = dstd = NULL: pmlp_reduce_slabs_step finishes the loss)
-        hipLaunchKernelGGL(k_ppo_loss_step_final, dim3(3 + A), dim3(64), 0, (hipStream_t)stream, a, partial, nb,
-                           stats, dstd);
-    PMLP_CHECK_LAUNCH("pmlp_ppo_loss_step");
-    return 0;
-}
-
-PMLP_API int pmlp_ppo_loss_step(const float* mu, const float* stdv, const float* value, const float* actions,
-                                const float* old_logp, const float* old_mu, const float* old_sigma, const float* adv,
-                                const float* ret, const float* target, const int64_t* rows, int32_t M, int32_t A,
-                                float clip, int32_t clipped_value, float vcoef, float ecoef, float* partial,
-                                float* stats, float* dstd, pmlp_bf16* dmu, pmlp_bf16* dmu_t, int32_t Ap,
-                                pmlp_bf16* dvalue, pmlp_bf16* dvalue_t, int32_t Vp, void* stream) {
-    LossArgs a;
-    if (int e = loss_args(a, mu, stdv, value, actions, old_logp, old_mu, old_sigma, adv, ret, target, rows, M, A, clip,
-                          clipped_value, vcoef, ecoef))
-        return e;
-    if (!partial || (!stats != !dstd) || !dmu || !dvalue || Ap < A || Vp < 1)
-        return fail(-1, "pmlp_ppo_loss_step: null output or padded width too small");
-    LossStepOut o{partial, (bf16*)dmu, (bf16*)dmu_t, (bf16*)dvalue, (bf16*)dvalue_t, Ap, Vp, nullptr, nullptr};
-    return loss_step_launch(a, o, M, A, Ap, partial, stats, dstd, stream);
-}
-
 PMLP_API int32_t pmlp_mlp_forward_ppo_loss_parts(int32_t M, int32_t A) {
     return (M >= 96 * 192 && A > 0 && A % 4 == 0 && A <= 16) ? ((M + 95) / 96) * (3 + A) : 0;
 }
@@ -3243,23 +2558,6 @@ PMLP_API int pmlp_mlp_forward_ppo_loss(const pmlp_mlp_fwd_job* jobs, int32_t M, 
                            (hipStream_t)stream, fj, M, none, a, o);
     PMLP_CHECK_LAUNCH("pmlp_mlp_forward_ppo_loss");
     return 0;
-}
-
-PMLP_API int pmlp_ppo_loss_step_f32(const float* mu, const float* stdv, const float* value, const float* actions,
-                                    const float* old_logp, const float* old_mu, const float* old_sigma,
-                                    const float* adv, const float* ret, const float* target, const int64_t* rows,
-                                    int32_t M, int32_t A, float clip, int32_t clipped_value, float vcoef, float ecoef,
-                                    float* partial, float* stats, float* dstd, float* dmu, float* dvalue,
-                                    void* stream) {
-    LossArgs a;
-    if (int e = loss_args(a, mu, stdv, value, actions, old_logp, old_mu, old_sigma, adv, ret, target, rows, M, A, clip,
-                          clipped_value, vcoef, ecoef))
-        return e;
-    if (!partial || !dmu || !dvalue || (!stats) != (!dstd))
-        return fail(-1, "pmlp_ppo_loss_step_f32: null output (stats and dstd both set, or both NULL)");
-    if (A % 4 == 0 && ((uintptr_t)dmu & 15)) return fail(-1, "pmlp_ppo_loss_step_f32: dmu 16-byte aligned");
-    LossStepOut o{partial, nullptr, nullptr, nullptr, nullptr, 0, 0, dmu, dvalue};
-    return loss_step_launch(a, o, M, A, 0, partial, stats, dstd, stream);
 }
 
 
