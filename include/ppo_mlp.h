@@ -655,4 +655,31 @@ PMLP_API int64_t pmlp_obs_norm_scratch_bytes(int32_t D);
 PMLP_API int pmlp_obs_norm_step(int32_t njobs, const pmlp_obs_norm_job* jobs, int32_t N, int32_t update,
                                 int64_t until, double eps, void* stream);
 
+/* ---- mirrored rollout rows for PPO's symmetry augmentation (rsl_rl 2.x symmetry_cfg, data
+ * augmentation): one launch per PPO iteration writes the mirrored half of the flat rollout.
+ * Every job moves the same R rows, fp32:
+ *   dst[r, j] = sign[j] * src[r, perm[j]],  j < K      (a signed permutation of the columns)
+ *   sign == NULL: dst[r, j] = src[r, perm[j]];  perm == NULL: dst[r, j] = src[r, j] (a row copy).
+ * The product with a sign of +-1 is exact, so the result equals the table applied in any fp32
+ * arithmetic bit for bit (a zero times -1 is -0).  src and dst share the row stride ld >= K;
+ * nothing outside [R, K] of dst is written.  perm and sign are device tables [K]; perm_host is
+ * the host copy of perm the checks read (the device table cannot be read before the launch
+ * without a synchronisation, which a captured graph cannot hold).  K <= PMLP_MIRROR_MAX_K.
+ * One launch, no scratch, nothing to reset between calls: a captured graph replays it.
+ * Errors (text in pmlp_last_error), all before the launch: -1 bad argument (job count outside
+ * 1..PMLP_MIRROR_MAX_JOBS, R < 1, null rows, a sign without a permutation, a permutation
+ * without its host copy), -3 K outside 1..PMLP_MIRROR_MAX_K, -4 ld < K, -5 a perm entry outside
+ * 0..K-1, -6 the dst range overlaps the src range; -2 the launch itself failed.               */
+#define PMLP_MIRROR_MAX_K 1024
+#define PMLP_MIRROR_MAX_JOBS 16
+typedef struct pmlp_mirror_rows_job {
+    const float* src;         /* rows [R, K], row stride ld (read only)                    */
+    float* dst;               /* rows [R, K], row stride ld                                */
+    int32_t ld, K;
+    const int32_t* perm;      /* device [K] or NULL                                        */
+    const float* sign;        /* device [K] or NULL                                        */
+    const int32_t* perm_host; /* host copy of perm (required with perm)                    */
+} pmlp_mirror_rows_job;
+PMLP_API int pmlp_mirror_rows(int32_t njobs, const pmlp_mirror_rows_job* jobs, int64_t R, void* stream);
+
 #endif

@@ -1,6 +1,9 @@
 """Short training run of a task, printing the rollout's mean step reward and the mean
 episode length per iteration (evidence that a config learns, e.g. H1 with and without
-self-collision).  usage: python tools/learn_curve.py task iters envs [self_collisions(0/1|-)] [pgs_sweeps|-] [seed]"""
+self-collision).  usage: python tools/learn_curve.py task iters envs [self_collisions(0/1|-)] [pgs_sweeps|-] [seed]
+For an env with symmetry tables a last line gives the gait asymmetry of the trained
+policy: the mean absolute difference between the left legs' action means and the mirrored right
+legs', over an evaluation rollout of 200 steps of the deterministic policy."""
 import os
 import sys
 
@@ -37,6 +40,31 @@ def main(task, iters, n, selfc=None, sweeps=None, seed=None):
         ep = float(env._episode_length.float().mean())
         if it % 10 == 0 or it == iters - 1:
             print(f"it {it:4d} mean step reward {float(st.rewards.mean()):+.5f}  mean episode length {ep:7.1f}", flush=True)
+
+
+    gait_asymmetry(env, runner)
+
+
+def gait_asymmetry(env, runner, steps=200):
+    try:
+        perm, sign = env.symmetry_tables()[2]
+    except ValueError:
+        return
+    policy = runner.get_inference_policy(device=env.device)
+    perm_t = torch.as_tensor(perm, dtype=torch.long, device=env.device)
+    sign_t = torch.as_tensor(sign, device=env.device)
+    total = torch.zeros(env.num_actions, device=env.device)
+    with torch.inference_mode():
+        obs = env.get_observations()
+        for _ in range(steps):
+            actions = policy(obs)
+            total += actions.mean(0)
+            obs = env.step(actions)[0]
+    mean = total / steps
+    left = perm_t > torch.arange(len(perm), device=env.device)
+    diff = (mean - sign_t * mean[perm_t]).abs()[left]
+    print(f"gait asymmetry over {steps} evaluation steps: mean |left - mirrored right| action mean = "
+          f"{float(diff.mean()):.4f} (per left joint: {[round(float(d), 4) for d in diff]})", flush=True)
 
 
 if __name__ == "__main__":

@@ -2,9 +2,10 @@
 from legged_gym import LEGGED_GYM_ROOT_DIR, LEGGED_GYM_ENVS_DIR  # noqa: F401
 
 from legged_gym.envs.go2.go2_config import (GO2RobustAsymCfg, GO2RobustAsymCfgPPO, GO2RobustCfg, GO2RobustCfgPPO,
-                                            GO2RobustHistoryCfg, GO2RobustHistoryCfgPPO, GO2RoughCfg, GO2RoughCfgPPO,
-                                            GO2TerrainCfg, GO2TerrainCfgPPO, GO2TerrainRobustAsymCfg,
-                                            GO2TerrainRobustAsymCfgPPO, GO2TerrainRobustCfg, GO2TerrainRobustCfgPPO)
+                                            GO2RobustHistoryCfg, GO2RobustHistoryCfgPPO, GO2RobustSymCfgPPO,
+                                            GO2RoughCfg, GO2RoughCfgPPO, GO2TerrainCfg, GO2TerrainCfgPPO,
+                                            GO2TerrainRobustAsymCfg, GO2TerrainRobustAsymCfgPPO, GO2TerrainRobustCfg,
+                                            GO2TerrainRobustCfgPPO, GO2TerrainRobustSymCfgPPO)
 from legged_gym.envs.go2.go2_handstand_config import GO2HandstandCfg, GO2HandstandCfgPPO
 from legged_gym.envs.go2.go2_handstand_env import GO2HandstandEnv
 from legged_gym.envs.h1.h1_config import H1RoughCfg, H1RoughCfgPPO
@@ -25,6 +26,8 @@ task_registry.register("go2_robust_history", LeggedRobot, GO2RobustHistoryCfg(),
 task_registry.register("go2_terrain_robust", LeggedRobot, GO2TerrainRobustCfg(), GO2TerrainRobustCfgPPO())
 task_registry.register("go2_robust_asym", LeggedRobot, GO2RobustAsymCfg(), GO2RobustAsymCfgPPO())
 task_registry.register("go2_terrain_robust_asym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustAsymCfgPPO())
+task_registry.register("go2_robust_sym", LeggedRobot, GO2RobustAsymCfg(), GO2RobustSymCfgPPO())
+task_registry.register("go2_terrain_robust_sym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustSymCfgPPO())
 task_registry.register("go2_handstand", GO2HandstandEnv, GO2HandstandCfg(), GO2HandstandCfgPPO())
 task_registry.register("h1", H1Robot,H1RoughCfg(), H1RoughCfgPPO())
 task_registry.register("h1_2", H1_2Robot, H1_2RoughCfg(), H1_2RoughCfgPPO())

@@ -31,7 +31,7 @@ from leggedsim import cabi, native
 from leggedsim.model import load_model
 from leggedsim.selfcollision import build_self_collision
 from leggedsim.task import (actuator_rand_params, build_task_params, check_scan_observations, height_obs_params,
-                            obs_history_params, priv_params, terrain_switches)
+                            obs_history_params, priv_params, symmetry_tables, terrain_switches)
 from legged_gym.utils.terrain import Terrain
 
 from .env_spec import derive_env_spec
@@ -420,6 +420,12 @@ class LeggedRobot(BaseTask):
         override returns the vector the kernel's observation noise then uses (task params)."""
         self.add_noise = self.cfg.noise.add_noise
         return torch.tensor(self.spec.noise_scale_vec, device=self.device)
+
+    def symmetry_tables(self):
+        """The left-right reflection of this env's policy, critic and action rows as signed
+        permutations (leggedsim/task.py symmetry_tables): what PPO's symmetry
+        augmentation (train cfg algorithm.symmetry_cfg) mirrors the rollout with."""
+        return symmetry_tables(self)
 
     # ------------------------------------------- per-step Python hooks -----
     # The native step has done each of these when a task override runs (the override's

@@ -232,6 +232,14 @@ class LeggedRobotCfgPPO(BaseConfig):
         desired_kl = 0.01
         max_grad_norm = 1.0
 
+        # left-right symmetry (rsl_rl 2.x's names).  use_data_augmentation: every
+        # mini-batch is trained together with its mirror image, built from the env's
+        # symmetry_tables().  use_mirror_loss is refused (not built yet).
+        class symmetry_cfg:
+            use_data_augmentation = False
+            use_mirror_loss = False
+            mirror_loss_coeff = 0.0
+
     class runner:
         policy_class_name = "ActorCritic"
         algorithm_class_name = "PPO"

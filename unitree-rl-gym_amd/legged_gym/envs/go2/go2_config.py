@@ -156,3 +156,26 @@ class GO2RobustAsymCfgPPO(GO2RobustHistoryCfgPPO):
 class GO2TerrainRobustAsymCfgPPO(GO2TerrainRobustCfgPPO):
     class runner(GO2TerrainRobustCfgPPO.runner):
         experiment_name = "go2_terrain_robust_asym"
+
+
+class GO2RobustSymCfgPPO(GO2RobustAsymCfgPPO):
+    """go2_robust_sym: go2_robust_asym trained with symmetry augmentation: every
+    mini-batch together with its left-right mirror image."""
+
+    class algorithm(GO2RobustAsymCfgPPO.algorithm):
+        class symmetry_cfg(GO2RobustAsymCfgPPO.algorithm.symmetry_cfg):
+            use_data_augmentation = True
+
+    class runner(GO2RobustAsymCfgPPO.runner):
+        experiment_name = "go2_robust_sym"
+
+
+class GO2TerrainRobustSymCfgPPO(GO2TerrainRobustAsymCfgPPO):
+    """go2_terrain_robust_sym: go2_terrain_robust_asym with symmetry augmentation."""
+
+    class algorithm(GO2TerrainRobustAsymCfgPPO.algorithm):
+        class symmetry_cfg(GO2TerrainRobustAsymCfgPPO.algorithm.symmetry_cfg):
+            use_data_augmentation = True
+
+    class runner(GO2TerrainRobustAsymCfgPPO.runner):
+        experiment_name = "go2_terrain_robust_sym"

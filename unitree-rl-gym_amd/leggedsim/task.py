@@ -423,3 +423,159 @@ def _native_task_switches(T, env, A):
         T.contact_flag_threshold = hs.contact_flag_threshold
         T.contact_flip_prob = hs.contact_flip_prob
         T.feet_together_target = hs.feet_together_target
+
+
+# ----------------------------------------------------------------- symmetry ----
+def scan_points(cfg):
+    """The height scan's points [P, 3] in the robot's yaw frame, in the order of the scan's entries
+    (legged_gym's _init_height_points: point k = ix * len(measured_points_y) + iy, z = 0)."""
+    tc = cfg.terrain
+    x, y = np.asarray(tc.measured_points_x, np.float64), np.asarray(tc.measured_points_y, np.float64)
+    gx, gy = np.meshgrid(x, y, indexing="ij")
+    return np.stack([gx.reshape(-1), gy.reshape(-1), np.zeros(gx.size)], axis=1)
+
+
+def _zero_pose_frames(model):
+    """World rotation and origin of every body's joint frame with every joint at zero."""
+    B = model.num_bodies
+    rot, pos = np.zeros((B, 3, 3)), np.zeros((B, 3))
+    for b in range(B):
+        jr = np.asarray(model.joint_rot[b], np.float64).reshape(3, 3)
+        jp = np.asarray(model.joint_pos[b], np.float64)
+        p = int(model.parent[b])
+        if p < 0:
+            rot[b], pos[b] = jr, jp
+        else:
+            rot[b], pos[b] = rot[p] @ jr, pos[p] + rot[p] @ jp
+    return rot, pos
+
+
+def joint_symmetry(env, tol=1e-4):
+    """The joint table of the reflection across the robot's sagittal (x-z) plane:
+    (perm int32 [D], sign float32 [D]) with mirror(q)[j] = sign[j] * q[perm[j]].  DOF j pairs with
+    the DOF whose joint origin, all joints at zero, is j's with y -> -y (a joint in the plane
+    pairs with itself), and whose axis is j's mirrored: a rotation about a mirrors to a rotation
+    about (-ax, ay, -az), so the pair's axes agree up to that map and a sign, and that sign is the
+    table's: -1 for an x or z axis, +1 for a y axis.  Refused: a model that does not pair
+    completely, and a cfg whose default pose, PD gains or action scale are not the mirror image of
+    themselves (the observation subtracts the default pose and the action is scaled into a PD
+    target around it, so the row's mirror would not be a signed permutation)."""
+    model = env.model
+    D = model.num_dofs
+    names = list(model.dof_names)
+    rot, pos = _zero_pose_frames(model)
+    body = [int(b) for b in model.dof_body]
+    org = np.array([pos[b] for b in body])
+    axw = np.array([rot[b] @ np.asarray(model.axis[b], np.float64) for b in body])
+    perm, sign = np.zeros(D, np.int32), np.zeros(D, np.float32)
+    for j in range(D):
+        want = org[j] * (1.0, -1.0, 1.0)
+        hits = [k for k in range(D) if np.abs(org[k] - want).max() < tol]
+        if len(hits) != 1:
+            raise ValueError(f"symmetry: joint {names[j]} has {len(hits)} mirror partners across the sagittal plane "
+                             "(the model does not pair left-right)")
+        k = hits[0]
+        m = axw[k] * (-1.0, 1.0, -1.0)  # the partner's rotation, mirrored
+        if np.abs(m - axw[j]).max() < tol:
+            s = 1.0
+        elif np.abs(m + axw[j]).max() < tol:
+            s = -1.0
+        else:
+            raise ValueError(f"symmetry: the axes of joints {names[j]} and {names[k]} are not mirror images")
+        perm[j], sign[j] = k, s
+    if not (perm[perm] == np.arange(D)).all() or not (sign * sign[perm] == 1).all():
+        raise ValueError("symmetry: the joint pairing is not an involution")
+    f = lambda v: np.asarray(_np(v), np.float64).reshape(-1)  # noqa: E731
+
+    def check(what, v, signed):
+        v = f(v)
+        m = v[perm] * (sign if signed else 1.0)
+        bad = np.nonzero(np.abs(m - v) > 1e-6 * np.maximum(1.0, np.abs(v)))[0]
+        if len(bad):
+            j = int(bad[0])
+            raise ValueError(f"symmetry: {what} of joint {names[j]} ({v[j]:g}) is not the mirror image of "
+                             f"{names[int(perm[j])]}'s ({v[int(perm[j])]:g})")
+
+    check("the default angle (init_state.default_joint_angles)", env.default_dof_pos, True)
+    check("the stiffness (control.stiffness)", env.p_gains, False)
+    check("the damping (control.damping)", env.d_gains, False)
+    scale = np.broadcast_to(f(env.cfg.control.action_scale), (D,)) if np.ndim(env.cfg.control.action_scale) == 0 \
+        else f(env.cfg.control.action_scale)
+    check("the action scale (control.action_scale)", scale, False)
+    return perm, sign
+
+
+def _scan_symmetry(cfg):
+    """The scan's table: point (x_i, y_j) -> (x_i, -y_j), sign +1, found on the point list."""
+    pts = scan_points(cfg)
+    P = len(pts)
+    perm = np.zeros(P, np.int32)
+    for k in range(P):
+        want = pts[k] * (1.0, -1.0, 1.0)
+        hits = np.nonzero(np.abs(pts - want).max(axis=1) < 1e-9)[0]
+        if len(hits) != 1:
+            raise ValueError(f"symmetry: terrain.measured_points_y is not symmetric about 0 (the scan point "
+                             f"({pts[k][0]:g}, {pts[k][1]:g}) has no mirror image)")
+        perm[k] = hits[0]
+    return perm, np.ones(P, np.float32)
+
+
+def _cat(*tables):
+    """Tables laid side by side: each block's permutation offset by the widths before it."""
+    perm, sign, off = [], [], 0
+    for p, s in tables:
+        perm.append(np.asarray(p, np.int64) + off)
+        sign.append(np.asarray(s, np.float32))
+        off += len(p)
+    return np.concatenate(perm).astype(np.int32), np.concatenate(sign).astype(np.float32)
+
+
+def symmetry_tables(env):
+    """The reflection across the robot's sagittal plane as signed permutations of the env's rows
+    (DESIGN 3.19): ((perm, sign) of the policy row, of the critic row, of the action row), each
+    perm int32 [K], sign float32 [K], mirror(x)[j] = sign[j] * x[perm[j]].  The critic row's table
+    is the policy row's when the env has no privileged row.  Quadruped layout only: the frame is
+    lin vel (+,-,+), ang vel (-,+,-), gravity (+,-,+), commands (+,-,-), then joint positions,
+    velocities and previous actions through joint_symmetry; an observation history tiles it; the
+    scan maps (x, y) -> (x, -y); the privileged row (3.17) is the clean frame, friction, added mass,
+    the per-joint kp, kd and strength factors permuted by the pairing with sign +1, the delay, and
+    the clean scan.  Refused: the handstand and the humanoid layouts, a task class with a Python
+    compute_observations, and what joint_symmetry and the scan's table refuse."""
+    if env.obs_layout == cabi.OBS_HANDSTAND:
+        raise ValueError("symmetry: the handstand layout is not supported (its pose target and front-feet terms "
+                         "are one-sided)")
+    if env.obs_layout == cabi.OBS_HUMANOID:
+        raise ValueError("symmetry: the humanoid layout is not supported yet (its registered tasks train "
+                         "recurrent policies, which the augmentation refuses)")
+    if env.obs_layout != cabi.OBS_QUADRUPED:
+        raise ValueError("symmetry: unknown observation layout")
+    if "compute_observations" in getattr(env, "_hooks", frozenset()):
+        raise ValueError("symmetry: the task class overrides compute_observations in Python, so its rows are not "
+                         "the layout's to describe")
+    A = env.num_actions
+    joints = joint_symmetry(env)
+    if len(joints[0]) != A:
+        raise ValueError("symmetry: num_actions must equal the number of DOFs")
+    ident3 = np.arange(3)
+    base = _cat((ident3, (1, -1, 1)), (ident3, (-1, 1, -1)), (ident3, (1, -1, 1)), (ident3, (1, -1, -1)))
+    frame = _cat(base, joints, joints, joints)
+    H = obs_history_params(env).frames if obs_history_params(env).enabled else 1
+    P = check_scan_observations(env.cfg, env.obs_layout, A)
+    scan = [_scan_symmetry(env.cfg)] if P else []
+    policy = _cat(*([frame] * H + scan))
+    if len(policy[0]) != env.num_obs:
+        raise ValueError(f"symmetry: the policy row's table has {len(policy[0])} entries for {env.num_obs} observations")
+    critic = policy
+    if env.num_privileged_obs:
+        R = priv_params(env)
+        if not R.enabled:
+            raise ValueError("symmetry: a privileged row without env.privileged_parameters is not the layout's "
+                             "to describe")
+        one = (np.zeros(1, np.int32), np.ones(1, np.float32))
+        unsigned = (joints[0], np.ones(A, np.float32))
+        tail = [one, one] + ([unsigned, unsigned, unsigned, one] if R.num_tail > 2 else [])
+        critic = _cat(frame, *tail, *scan)
+        if len(critic[0]) != env.num_privileged_obs:
+            raise ValueError(f"symmetry: the critic row's table has {len(critic[0])} entries for "
+                             f"{env.num_privileged_obs} privileged observations")
+    return policy, critic, joints

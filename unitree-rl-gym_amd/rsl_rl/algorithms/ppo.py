@@ -38,8 +38,14 @@ class PPO:
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", fused_loss=True):
+                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", fused_loss=True,
+                 symmetry_cfg=None, symmetry_tables=None):
+        """symmetry_cfg (rsl_rl 2.x's keys use_data_augmentation, use_mirror_loss, mirror_loss_coeff;
+        None: off) with symmetry_tables, the env's (policy row, critic row, action row) signed
+        permutations (LeggedRobot.symmetry_tables(); OnPolicyRunner passes them): every mini-batch
+        is trained together with its mirror image."""
         self.device = device
+        self._sym = self._symmetry(actor_critic, symmetry_cfg, symmetry_tables)
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.actor_critic = actor_critic
@@ -108,6 +114,40 @@ class PPO:
             for p in params:  # identical initial policy on every rank
                 dist.broadcast(p.data, src=0)
 
+    SYMMETRY_KEYS = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff")
+
+    def _symmetry(self, actor_critic, cfg, tables):
+        """The (policy, critic, action) SignedPermutations of symmetry_cfg's data augmentation, or
+        None when it is off; the refusals of DESIGN 3.19."""
+        cfg = dict(cfg or {})
+        unknown = sorted(set(cfg) - set(self.SYMMETRY_KEYS))
+        if unknown:
+            raise ValueError(f"symmetry_cfg: unknown keys {unknown} (known: {list(self.SYMMETRY_KEYS)})")
+        if cfg.get("use_mirror_loss", False):
+            raise ValueError("symmetry_cfg.use_mirror_loss is not supported: the mirror loss couples a row to its "
+                             "mirror image inside the loss kernels; use use_data_augmentation")
+        if not cfg.get("use_data_augmentation", False):
+            return None
+        if getattr(actor_critic, "is_recurrent", False):
+            raise ValueError("symmetry_cfg.use_data_augmentation is not supported for recurrent policies (a mirrored "
+                             "sequence needs mirrored hidden states)")
+        if tables is None:
+            raise ValueError("symmetry_cfg.use_data_augmentation needs symmetry_tables: the env's "
+                             "symmetry_tables() (OnPolicyRunner passes them)")
+        if len(tables) != 3:
+            raise ValueError("symmetry_tables: (policy row, critic row, action row) tables")
+        return tuple(mfma_mlp.SignedPermutation(p, sg, self.device) for p, sg in tables)
+
+    def _augment(self, obs, cobs, actions, values, adv, ret, logp, mu, sigma):
+        """A mini-batch followed by its mirror image, in torch: observations, actions and the old
+        mean through their tables, the old sigma through the action permutation alone, and the
+        values, advantages, returns and old log-probabilities repeated (rsl_rl 2.x)."""
+        so, sc, sa = self._sym
+        cat, rep2 = torch.cat, lambda t: torch.cat([t, t])  # noqa: E731
+        return (cat([obs, so.mirror_torch(obs)]), cat([cobs, sc.mirror_torch(cobs)]),
+                cat([actions, sa.mirror_torch(actions)]), rep2(values), rep2(adv), rep2(ret), rep2(logp),
+                cat([mu, sa.mirror_torch(mu)]), cat([sigma, sigma.index_select(-1, sa.index)]))
+
     # learning_rate is read by the runner's logger (rsl_rl attribute)
     @property
     def learning_rate(self):
@@ -121,13 +161,20 @@ class PPO:
                 g["lr"] = float(v)
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        sym = self._sym is not None
+        if sym:
+            widths = (actor_obs_shape[0], critic_obs_shape[0] if critic_obs_shape[0] is not None else
+                      actor_obs_shape[0], action_shape[0])
+            if tuple(t.K for t in self._sym) != tuple(widths):
+                raise ValueError(f"symmetry_tables of widths {[t.K for t in self._sym]} for rows of {list(widths)}")
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape,
-                                      action_shape, self.device)
+                                      action_shape, self.device, mirrored_half=sym)
         batch = num_envs * num_transitions_per_env
         if self._fused_loss and not self.actor_critic.is_recurrent and self._fused is None and \
                 getattr(self.actor_critic, "mixed_precision", False) and batch % self.num_mini_batches == 0:
             try:  # whole optimizer step in ~20 launches (algorithms/fused_step.py)
-                self._fused = fused_step.FusedPPOStep(self, batch // self.num_mini_batches)
+                # (with the symmetry augmentation a mini-batch is its rows and their mirror images)
+                self._fused = fused_step.FusedPPOStep(self, batch // self.num_mini_batches * (2 if sym else 1))
                 self._rollout = fused_step.FusedRollout(self._fused, num_envs) if num_envs % 8 == 0 else None
             except ValueError:
                 self._fused = self._rollout = None
@@ -352,6 +399,11 @@ class PPO:
                         masks_batch, acc):
         """One PPO optimizer step on one mini-batch (rsl_rl v1.0.2 PPO.update body)."""
         recurrent = self.actor_critic.is_recurrent
+        if self._sym is not None:  # the mini-batch and its mirror image; every mean below is over both
+            (obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
+             old_actions_log_prob_batch, old_mu_batch, old_sigma_batch) = self._augment(
+                obs_batch, critic_obs_batch, actions_batch, target_values_batch, advantages_batch, returns_batch,
+                old_actions_log_prob_batch, old_mu_batch, old_sigma_batch)
         if self._fused_loss and (not recurrent or self._dense_recurrent):
             # same loss, two fused kernels forward + two backward (modules/mfma_mlp.ppo_loss)
             if recurrent:  # dense form: every [T, envs, .] tensor flattened to T*envs rows
@@ -457,28 +509,46 @@ class PPO:
         f, st = self._fused, self.storage
         f.sync_optimizer_state(self.optimizer)
         f.ensure_weights()  # the captured steps read the bf16 weight copies from the first one
-        mb = f.M
+        sym = self._sym is not None
+        mb = f.M // 2 if sym else f.M
+        nmb = self.num_mini_batches
         if self._fgraph is None and not hasattr(self, "_fperm"):
-            self._fperm = torch.empty(self.num_mini_batches * mb, dtype=torch.int64, device=self.device)
+            self._fperm = torch.empty(nmb * mb, dtype=torch.int64, device=self.device)
             self._facc = torch.zeros(2, device=self.device)
-            cobs = st.privileged_observations if st.privileged_observations is not None else st.observations
-            self._fsrc = (st.observations.flatten(0, 1), cobs.flatten(0, 1) if cobs is not st.observations
-                          else st.observations.flatten(0, 1), st.actions.flatten(0, 1), st.values.flatten(0, 1),
-                          st.advantages.flatten(0, 1), st.returns.flatten(0, 1), st.actions_log_prob.flatten(0, 1),
-                          st.mu.flatten(0, 1), st.sigma.flatten(0, 1))
+            names = ("observations", "privileged_observations", "actions", "values", "advantages", "returns",
+                     "actions_log_prob", "mu", "sigma")
+            # (with the symmetry augmentation: the doubled allocations, rows B .. 2B-1 the mirror images)
+            whole = (lambda n: st.doubled.get(n)) if sym else (lambda n: getattr(st, n))
+            self._fsrc = tuple(None if whole(n) is None else whole(n).flatten(0, 1) for n in names)
             if st.privileged_observations is None:  # the critic reads the actor's observations
                 self._fsrc = (self._fsrc[0], self._fsrc[0]) + self._fsrc[2:]
             self._fadv = st.advantages
+            if sym:
+                # each mini-batch's index is [perm_i, perm_i + B]; the mirror launch's jobs write
+                # rows B .. 2B-1 of every tensor from rows 0 .. B-1
+                B = nmb * mb
+                self._fidx = torch.empty(nmb, 2 * mb, dtype=torch.int64, device=self.device)
+                so, sc, sa = self._sym
+                tabs = (so, sc, sa, None, None, None, None, sa, sa.unsigned())
+                self._fmirror = [(t[:B], t[B:], tab) for k, (t, tab) in enumerate(zip(self._fsrc, tabs))
+                                 if not (k == 1 and st.privileged_observations is None)]
         if st.advantages.data_ptr() != self._fadv.data_ptr():
             self._fadv.copy_(st.advantages)
             st.advantages = self._fadv
         mfma_mlp.permutation_(self._fperm)  # as minibatch_permutation (no device sort)
+        if sym:  # outside the graph, where the permutation is drawn
+            pv = self._fperm.view(nmb, mb)
+            self._fidx[:, :mb].copy_(pv)
+            torch.add(pv, nmb * mb, out=self._fidx[:, mb:])
 
         def body():
+            if sym:  # GAE and the normalisation have written the first half: now its mirror image
+                mfma_mlp.mirror_rows(self._fmirror, nmb * mb)
             self._facc.zero_()
             for _ in range(self.num_learning_epochs):
-                for i in range(self.num_mini_batches):
-                    f.run(self._fperm[i * mb:(i + 1) * mb], self._fsrc, self._facc)
+                for i in range(nmb):
+                    rows = self._fidx[i] if sym else self._fperm[i * mb:(i + 1) * mb]
+                    f.run(rows, self._fsrc, self._facc)
 
         if not (self.use_graph and self._graph_calls >= 2):
             body()

@@ -117,7 +117,14 @@ class ObsNormJob(C.Structure):
                 ("inv32", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class MirrorRowsJob(C.Structure):
+    """include/ppo_mlp.h pmlp_mirror_rows_job (pmlp_mirror_rows)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("ld", C.c_int32), ("K", C.c_int32),
+                ("perm", C.c_void_p), ("sign", C.c_void_p), ("perm_host", C.POINTER(C.c_int32))]
+
+
 MAX_JOBS, MAX_GEMM_JOBS = 16, 4
+PMLP_MIRROR_MAX_JOBS, PMLP_MIRROR_MAX_K = 16, 1024  # include/ppo_mlp.h
 PMLP_MAX_MIRROR = 8  # include/ppo_mlp.h: bf16 weight copies one Adam launch writes
 
 
@@ -186,6 +193,7 @@ def load():
         L.pmlp_obs_norm_scratch_bytes.argtypes = [i32]
         L.pmlp_obs_norm_scratch_bytes.restype = i64
         L.pmlp_obs_norm_step.argtypes = [i32, C.POINTER(ObsNormJob), i32, i32, i64, C.c_double, vp]
+        L.pmlp_mirror_rows.argtypes = [i32, C.POINTER(MirrorRowsJob), i64, vp]
         _lib = L
     return _lib
 
@@ -346,6 +354,51 @@ def obs_norm_step(jobs, N, update, until, eps):
     if status != 0:
         raise RuntimeError(f"pmlp_obs_norm_step failed ({status}): "
                            f"{load().pmlp_obs_norm_last_error().decode(errors='replace')}")
+
+
+class SignedPermutation:
+    """A signed permutation of K columns, mirror(x)[j] = sign[j] * x[perm[j]], as pmlp_mirror_rows
+    takes it: the int32 / fp32 device tables and the host copy of perm its checks read.  sign
+    None: +1 everywhere.  `index` (int64) and `sign_t` are the same tables for torch's
+    index_select statement of the mirror (mirror_torch)."""
+
+    def __init__(self, perm, sign, device):
+        import numpy as np
+        self.perm_np = np.ascontiguousarray(np.asarray(perm, dtype=np.int32).reshape(-1))
+        self.K = int(self.perm_np.shape[0])
+        self.sign_np = None if sign is None else np.ascontiguousarray(np.asarray(sign, dtype=np.float32).reshape(-1))
+        if self.sign_np is not None and self.sign_np.shape[0] != self.K:
+            raise ValueError("signed permutation: perm and sign differ in length")
+        self.perm_host = self.perm_np.ctypes.data_as(C.POINTER(C.c_int32))
+        self.perm = torch.from_numpy(self.perm_np).to(device)
+        self.sign = None if self.sign_np is None else torch.from_numpy(self.sign_np).to(device)
+        self.index = self.perm.to(torch.int64)
+
+    def unsigned(self):
+        """The same permutation with sign +1 (a standard deviation's mirror)."""
+        return SignedPermutation(self.perm_np, None, self.perm.device)
+
+    def mirror_torch(self, x):
+        y = x.index_select(-1, self.index)
+        return y if self.sign is None else y * self.sign
+
+
+def mirror_rows(jobs, R):
+    """pmlp_mirror_rows: one launch writing dst[r, j] = sign[j] * src[r, perm[j]] for every job
+    (src, dst, table) over the same R rows; src and dst are fp32 [>= R, K] tensors of one row
+    stride, table a SignedPermutation or None (a row copy)."""
+    def mk(j):
+        src, dst, tab = j
+        K = src.shape[-1] if src.dim() > 1 else 1
+        ld = src.stride(0) if src.dim() > 1 else 1
+        if dst.dtype != torch.float32 or src.dtype != torch.float32 or (dst.stride(0) if dst.dim() > 1 else 1) != ld:
+            raise ValueError("mirror_rows: fp32 rows of one row stride")
+        if tab is not None and tab.K != K:
+            raise ValueError(f"mirror_rows: a table of {tab.K} entries for rows of {K}")
+        return MirrorRowsJob(_p(src), _p(dst), ld, K, None if tab is None else _p(tab.perm),
+                             None if tab is None else _p(tab.sign), None if tab is None else tab.perm_host)
+    arr = (MirrorRowsJob * len(jobs))(*[mk(j) for j in jobs])
+    _ok(load().pmlp_mirror_rows(len(jobs), arr, int(R), _stream()), "pmlp_mirror_rows")
 
 
 def permutation_(out):

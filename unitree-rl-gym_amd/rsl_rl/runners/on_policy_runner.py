@@ -128,7 +128,17 @@ class OnPolicyRunner:
         actor_critic = actor_critic_class(self.env.num_obs, num_critic_obs, self.env.num_actions,
                                           **self.policy_cfg).to(self.device)
         alg_class = eval(self.cfg["algorithm_class_name"])
-        self.alg: PPO = alg_class(actor_critic, device=self.device, **self.alg_cfg)
+        alg_kwargs = dict(self.alg_cfg)
+        if (alg_kwargs.get("symmetry_cfg") or {}).get("use_data_augmentation", False):
+            # the mirror images come from the env's own description of its rows
+            if self.cfg.get("empirical_normalization", False):
+                raise ValueError("symmetry_cfg.use_data_augmentation with empirical_normalization is not supported: "
+                                 "the storage holds normalised rows, whose mirror image is a signed permutation "
+                                 "only under symmetrised statistics")
+            if not hasattr(self.env, "symmetry_tables"):
+                raise ValueError("symmetry_cfg.use_data_augmentation needs an env with symmetry_tables()")
+            alg_kwargs["symmetry_tables"] = self.env.symmetry_tables()
+        self.alg: PPO = alg_class(actor_critic, device=self.device, **alg_kwargs)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(self.env.num_envs, self.num_steps_per_env, [self.env.num_obs],

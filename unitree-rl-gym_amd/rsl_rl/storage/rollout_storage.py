@@ -33,26 +33,44 @@ class RolloutStorage:
         def clear(self):
             self.__init__()
 
-    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device="cpu"):
+    # the tensors a PPO mini-batch reads: with `mirrored_half` each is allocated once with 2T
+    # leading rows, the attribute being the first T and `doubled[name]` the whole
+    DOUBLED = ("observations", "privileged_observations", "actions", "actions_log_prob", "values", "returns",
+               "advantages", "mu", "sigma")
+
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device="cpu",
+                 mirrored_half=False):
+        """mirrored_half (PPO's symmetry augmentation): rows T .. 2T-1 of every `DOUBLED` tensor
+        hold the mirror image of rows 0 .. T-1, written once per update; the attributes keep
+        today's names, shapes and contiguity (the first T rows), so the rollout, GAE and
+        get_statistics see nothing new.  Off: today's allocation."""
         self.device = device
         self.obs_shape = obs_shape
         self.privileged_obs_shape = privileged_obs_shape
         self.actions_shape = actions_shape
         T, N = num_transitions_per_env, num_envs
-        self.observations = torch.zeros(T, N, *obs_shape, device=device)
+        self.doubled = {} if mirrored_half else None
+
+        def rows(name, *shape):
+            if not mirrored_half:
+                return torch.zeros(T, N, *shape, device=device)
+            self.doubled[name] = torch.zeros(2 * T, N, *shape, device=device)
+            return self.doubled[name][:T]
+
+        self.observations = rows("observations", *obs_shape)
         if privileged_obs_shape[0] is not None:
-            self.privileged_observations = torch.zeros(T, N, *privileged_obs_shape, device=device)
+            self.privileged_observations = rows("privileged_observations", *privileged_obs_shape)
         else:
             self.privileged_observations = None
         self.rewards = torch.zeros(T, N, 1, device=device)
-        self.actions = torch.zeros(T, N, *actions_shape, device=device)
+        self.actions = rows("actions", *actions_shape)
         self.dones = torch.zeros(T, N, 1, device=device).byte()
-        self.actions_log_prob = torch.zeros(T, N, 1, device=device)
-        self.values = torch.zeros(T, N, 1, device=device)
-        self.returns = torch.zeros(T, N, 1, device=device)
-        self.advantages = torch.zeros(T, N, 1, device=device)
-        self.mu = torch.zeros(T, N, *actions_shape, device=device)
-        self.sigma = torch.zeros(T, N, *actions_shape, device=device)
+        self.actions_log_prob = rows("actions_log_prob", 1)
+        self.values = rows("values", 1)
+        self.returns = rows("returns", 1)
+        self.advantages = rows("advantages", 1)
+        self.mu = rows("mu", *actions_shape)
+        self.sigma = rows("sigma", *actions_shape)
         self.num_transitions_per_env = T
         self.num_envs = N
         self.saved_hidden_states_a = None
