@@ -136,6 +136,19 @@ def test_rng_identical_in_product_and_oracle(oracle_lib):
         assert a == b and 0.0 <= a < 1.0
 
 
+def test_product_rng_rests_on_the_known_answers():
+    """lgs_uniform (the env step's philox_uniform on the host) == act_ref.uniform_ref, which
+    test_act_ref_host.py ties to the published Philox4x32-10 vectors: the seed's high word set,
+    every counter word at 0 and 0xffffffff."""
+    import torch  # noqa: F401  (shared HIP runtime before loading the product lib)
+    import act_ref
+    from leggedsim import native
+    lib = native.load()
+    for seed, *args in act_ref.uniform_cases():
+        got = np.float32(lib.lgs_uniform(seed, *args))
+        assert got == act_ref.uniform_ref(seed, *args) and 0.0 <= got < 1.0, (hex(seed), args)
+
+
 @pytest.mark.parametrize("task,ch", [("go2", 3), ("h1", 5), ("h1_2", 6)])
 def test_level_order_factorisation_is_the_same_solve(task, ch, oracle_lib):
     """orc_set_factor_chain(CH): the chain-structured kernels eliminate the joint pivots level by

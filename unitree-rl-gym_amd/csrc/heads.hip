@@ -146,7 +146,7 @@ __device__ __forceinline__ void span_store(int N, int r0, int M, const float (&v
 
 // pmlp_heads_forward_act: the rollout's pmlp_act in the heads' launch (job 0 the actor, job 1
 // the critic): each actor workgroup samples its rows' actions from the mu tile still in LDS
-// (act_quad: pmlp_act's arithmetic, the same bits) and writes the storage rows; the critic's
+// (act_quad: pmlp_act's sampling function, the same bits) and writes the storage rows; the critic's
 // workgroups write the values and privileged rows
 struct HeadAct {
     const float *stdv, *obs, *cobs;

@@ -1,7 +1,8 @@
-// The rollout's policy noise and Gaussian log-density, shared by pmlp_act (ppo_mlp.hip), the
-// fused rollout forward and the recurrent heads' fused sampling (heads.hip), so all of them
-// compute the same bits: Philox4x32-10 keyed by the rollout seed, counter (draw, env row,
-// action quad, 0x5050), Box-Muller pairs (rsl_rl ActorCritic.act: Normal(mu, std).sample()).
+// The rollout's policy noise and Gaussian log-density: ONE statement of the sampling, act_quad,
+// called by pmlp_act's two kernels and the fused rollout forward (ppo_mlp.hip) and by the recurrent
+// heads' fused sampling (heads.hip), so all of them compute the same bits: Philox4x32-10 keyed by
+// the rollout seed, counter (draw, env row, action quad, 0x5050), Box-Muller pairs (rsl_rl
+// ActorCritic.act: Normal(mu, std).sample()).  tests/act_ref.py is its fp64 reference.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,11 +23,13 @@ __device__ __forceinline__ float u01(uint32_t x) { return ((float)x + 0.5f) * 2.
 
 static constexpr float kHalfLog2Pi = 0.91893853320467274f;  // log(sqrt(2 pi))
 
-// pmlp_act's sampling of row i, actions 4c .. 4c + 3 (k < A): act = mu + sigma z and the
-// Gaussian log-density term of each (the caller sums a row's terms into its log-probability)
+// The sampling of row i, actions 4c .. 4c + 3 (k < A): act = mu + sigma z and the Gaussian
+// log-density term of each (the caller sums a row's terms in k order into its log-probability).
+// Contraction is off inside, whatever the caller or the translation unit's flags say: mu + sigma z
+// is a rounded product and a rounded sum, as rsl_rl's mean + std * eps is, in every arm.
 __device__ __forceinline__ void act_quad(uint32_t draw, uint2 key, uint32_t i, int c, int A, const float* stdv,
                                          const float* mu, float act[4], float sg[4], float term[4]) {
-    // (the library's default contraction, as pmlp_act has always been compiled)
+#pragma clang fp contract(off)
     const uint4 r = philox4x32(make_uint4(draw, i, (uint32_t)c, 0x5050u), key);
     const float rad0 = sqrtf(-2.f * logf(u01(r.x))), rad1 = sqrtf(-2.f * logf(u01(r.z)));
     float z[4];

@@ -1430,8 +1430,8 @@ __device__ __forceinline__ void ex_once(const pmlp_env_extras& x, bool any, int 
 
 // The rollout's work on the workgroup's R rows after job jj's forward (its outputs are in
 // J.out, written by this workgroup before the barrier that precedes this call).  Job 0 (the
-// actor): sampling and the storage rows, k_act4's Philox counters and arithmetic; the
-// deferred store of the previous step.  Job 1 (the critic): the value and privileged rows.
+// actor): sampling (act_quad, pmlp_noise.h) and the storage rows; the deferred store of the
+// previous step.  Job 1 (the critic): the value and privileged rows.
 template <int R>
 __device__ void roll_epilogue(const FmlpJob& J, int jj, const RollStep& rs, int r0, int M, float* terms) {
 #pragma clang fp contract(off)
@@ -1442,26 +1442,20 @@ __device__ void roll_epilogue(const FmlpJob& J, int jj, const RollStep& rs, int 
         for (int q = tid; q < R * 4; q += FMLP_THREADS) {  // (row, action quad)
             const int rl = q >> 2, c = q & 3, k0 = 4 * c, i = r0 + rl;
             if (i >= M || k0 >= rs.A) continue;
-            const uint4 r = philox4x32(make_uint4(draw, (uint32_t)i, (uint32_t)c, 0x5050u), key);
-            const float rad0 = sqrtf(-2.f * logf(u01(r.x))), rad1 = sqrtf(-2.f * logf(u01(r.z)));
-            float z[4];
-            sincospif(2.f * u01(r.y), &z[1], &z[0]);
-            sincospif(2.f * u01(r.w), &z[3], &z[2]);
-            z[0] *= rad0; z[1] *= rad0; z[2] *= rad1; z[3] *= rad1;
+            float act[4], mu[4], sg[4], tm[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + u;
-                if (k >= rs.A) break;
-                const size_t o = (size_t)i * rs.A + k;
-                const float sg = rs.stdv[k], mu = J.out[(size_t)i * J.ldo + k];
-                const float act = mu + sg * z[u];
-                const float d = act - mu;
-                terms[rl * 16 + k] = -(d * d) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-                rs.actions_out[o] = act;
-                rs.st_actions[o] = act;
-                rs.st_mu[o] = mu;
-                rs.st_sigma[o] = sg;
-            }
+            for (int u = 0; u < 4; ++u) mu[u] = k0 + u < rs.A ? J.out[(size_t)i * J.ldo + k0 + u] : 0.f;
+            act_quad(draw, key, (uint32_t)i, c, rs.A, rs.stdv, mu, act, sg, tm);
+            const size_t o = (size_t)i * rs.A + k0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (k0 + u < rs.A) {
+                    terms[rl * 16 + k0 + u] = tm[u];
+                    rs.actions_out[o + u] = act[u];
+                    rs.st_actions[o + u] = act[u];
+                    rs.st_mu[o + u] = mu[u];
+                    rs.st_sigma[o + u] = sg[u];
+                }
         }
         __syncthreads();
         const bool ex = rs.rew && rs.ex.acc;
@@ -1678,26 +1672,20 @@ __global__ __launch_bounds__(256) void k_act(ActArgs a) {
     for (int64_t i = tid; i < a.N; i += nth) {
         float logp = 0.f;
         for (int k0 = 0; k0 < a.A; k0 += 4) {
-            const uint4 r = philox4x32(make_uint4(draw, (uint32_t)i, (uint32_t)(k0 >> 2), 0x5050u), key);
-            const float rad0 = sqrtf(-2.f * logf(u01(r.x))), rad1 = sqrtf(-2.f * logf(u01(r.z)));
-            float z[4];
-            sincospif(2.f * u01(r.y), &z[1], &z[0]);
-            sincospif(2.f * u01(r.w), &z[3], &z[2]);
-            z[0] *= rad0; z[1] *= rad0; z[2] *= rad1; z[3] *= rad1;
+            const size_t o = (size_t)i * a.A + k0;
+            float act[4], mu[4], sg[4], tm[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + u;
-                if (k >= a.A) break;
-                const size_t o = (size_t)i * a.A + k;
-                const float sg = a.stdv[k], mu = a.mu[o];
-                const float act = mu + sg * z[u];
-                const float d = act - mu;
-                logp += -(d * d) / (2.f * sg * sg) - logf(sg) - kHalfLog2Pi;
-                a.actions_out[o] = act;
-                a.st_actions[o] = act;
-                a.st_mu[o] = mu;
-                a.st_sigma[o] = sg;
-            }
+            for (int u = 0; u < 4; ++u) mu[u] = k0 + u < a.A ? a.mu[o + u] : 0.f;
+            act_quad(draw, key, (uint32_t)i, k0 >> 2, a.A, a.stdv, mu, act, sg, tm);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (k0 + u < a.A) {
+                    logp += tm[u];
+                    a.actions_out[o + u] = act[u];
+                    a.st_actions[o + u] = act[u];
+                    a.st_mu[o + u] = mu[u];
+                    a.st_sigma[o + u] = sg[u];
+                }
         }
         a.st_logp[i] = logp;
         a.st_value[i] = a.value[i];
