@@ -691,4 +691,48 @@ typedef struct pmlp_mirror_rows_job {
 } pmlp_mirror_rows_job;
 PMLP_API int pmlp_mirror_rows(int32_t njobs, const pmlp_mirror_rows_job* jobs, int64_t R, void* stream);
 
+/* ---- teacher-student distillation (rsl_rl 2.x Distillation, feed-forward student; csrc/distill.hip,
+ * DESIGN 3.20): the two scalar kernels around the library's GEMMs.
+ *
+ * pmlp_distill_act: Distillation.act for storage step t, after one pmlp_mlp_forward of two jobs
+ * (the student on obs[N,O], the teacher on the privileged row) has written mu[N,A] and mu_t[N,A]:
+ *   actions_out[N,A]       = mu + std * n, the sampling function of pmlp_act (csrc/pmlp_noise.h
+ *                            act_quad): bitwise pmlp_act's actions for equal (seed, draw, mu, std)
+ *   st_obs[N,O]            = obs          (bitwise copies: the storage rows of step t)
+ *   st_teacher_actions[N,A] = mu_t
+ *   draw[parity ^ 1]       = draw[parity] + 1   (pmlp_rollout_forward's scheme: the k-th act reads
+ *                            draw[k % 2], whose low 32 bits are the counter's draw word)
+ * A <= PMLP_DISTILL_ACT_MAX_A.  A % 4 == 0 with 16-byte aligned mu and actions_out: four lanes per
+ * row; else one lane per row (the same bits).  One launch, nothing to reset: a graph replays it.
+ * Errors: -1 bad argument, -3 A too large, -2 the launch failed.
+ *
+ * pmlp_distill_loss_step: the behaviour loss of ONE optimizer step, forward and backward, over
+ * the M = gradient_length * N contiguous storage rows of the step.  With d = mu - target per entry
+ * and scale = 1 / (N * A) (a step's loss is the mean over its N * A entries; the steps' losses add):
+ *   PMLP_DISTILL_MSE:   term = d * d,                 gradient = (2 d) * scale
+ *   PMLP_DISTILL_HUBER: |d| <= 1: term = (0.5 d) * d, gradient = d * scale
+ *     (delta = 1)       |d| >  1: term = |d| - 0.5,   gradient = sign(d) * scale
+ *   dmu_b[M,Ap] (bf16)  the gradient, straight into the backward GEMMs' operand; columns A .. Ap-1
+ *                       are written as zeros
+ *   dmu_f[M,A]  (fp32)  the same gradient before the bf16 rounding; optional (NULL)
+ *   partial[pmlp_distill_loss_parts(M)]  one per 64 rows: the sum of the rows' unscaled terms (a
+ *                       row's in k order, then the 64 rows' by a fixed butterfly)
+ *   stats[4]            stats[0] = (sum of the partials, in a fixed order) * scale, stats[1..3] = 0:
+ *                       the layout pmlp_opt_prepare accumulates with adaptive = 0 (acc[1] += stats[0])
+ * No atomics: two launches on the same inputs give the same bits.  A <= PMLP_DISTILL_LOSS_MAX_A,
+ * Ap a multiple of 8 with A <= Ap <= PMLP_DISTILL_LOSS_MAX_A, dmu_b 16-byte aligned.  Two launches
+ * (the rows, then a one-wave finish).  Errors: -1 bad argument, -3 A too large, -4 bad Ap, -5
+ * dmu_b misaligned, -2 a launch failed.                                                        */
+#define PMLP_DISTILL_ACT_MAX_A 16
+#define PMLP_DISTILL_LOSS_MAX_A 32
+#define PMLP_DISTILL_MSE 0
+#define PMLP_DISTILL_HUBER 1
+PMLP_API int pmlp_distill_act(const float* mu, const float* mu_t, const float* stdv, const float* obs, int32_t N,
+                              int32_t A, int32_t O, int64_t* draw, int32_t parity, uint64_t seed, float* actions_out,
+                              float* st_obs, float* st_teacher_actions, void* stream);
+PMLP_API int32_t pmlp_distill_loss_parts(int32_t M);
+PMLP_API int pmlp_distill_loss_step(const float* mu, const float* target, int32_t M, int32_t A, int32_t loss_type,
+                                    float scale, float* partial, float* stats, void* dmu_b, float* dmu_f, int32_t Ap,
+                                    void* stream);
+
 #endif

@@ -1,6 +1,9 @@
 """Task registration (reference envs/__init__.py:1-27): the plugin API."""
 from legged_gym import LEGGED_GYM_ROOT_DIR, LEGGED_GYM_ENVS_DIR  # noqa: F401
 
+from legged_gym.envs.go2.go2_config import (GO2RobustDistillCfgPPO, GO2RobustTeacherCfg, GO2RobustTeacherCfgPPO,
+                                            GO2TerrainRobustDistillCfgPPO, GO2TerrainRobustTeacherCfg,
+                                            GO2TerrainRobustTeacherCfgPPO)
 from legged_gym.envs.go2.go2_config import (GO2RobustAsymCfg, GO2RobustAsymCfgPPO, GO2RobustCfg, GO2RobustCfgPPO,
                                             GO2RobustHistoryCfg, GO2RobustHistoryCfgPPO, GO2RobustSymCfgPPO,
                                             GO2RoughCfg, GO2RoughCfgPPO, GO2TerrainCfg, GO2TerrainCfgPPO,
@@ -16,6 +19,7 @@ from legged_gym.envs.g1.g1_config import (G1GruCfgPPO, G1HeightfieldCfg, G1Rough
                                           G1TerrainScanCfg, G1TerrainScanCfgPPO)
 from legged_gym.envs.g1.g1_env import G1Robot
 from .base.legged_robot import LeggedRobot
+from .base.privileged_actor import PrivilegedActorRobot
 
 from legged_gym.utils.task_registry import task_registry
 
@@ -28,6 +32,12 @@ task_registry.register("go2_robust_asym", LeggedRobot, GO2RobustAsymCfg(), GO2Ro
 task_registry.register("go2_terrain_robust_asym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustAsymCfgPPO())
 task_registry.register("go2_robust_sym", LeggedRobot, GO2RobustAsymCfg(), GO2RobustSymCfgPPO())
 task_registry.register("go2_terrain_robust_sym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustSymCfgPPO())
+task_registry.register("go2_robust_teacher", PrivilegedActorRobot, GO2RobustTeacherCfg(), GO2RobustTeacherCfgPPO())
+task_registry.register("go2_terrain_robust_teacher", PrivilegedActorRobot, GO2TerrainRobustTeacherCfg(),
+                       GO2TerrainRobustTeacherCfgPPO())
+task_registry.register("go2_robust_distill", LeggedRobot, GO2RobustAsymCfg(), GO2RobustDistillCfgPPO())
+task_registry.register("go2_terrain_robust_distill", LeggedRobot, GO2TerrainRobustAsymCfg(),
+                       GO2TerrainRobustDistillCfgPPO())
 task_registry.register("go2_handstand", GO2HandstandEnv, GO2HandstandCfg(), GO2HandstandCfgPPO())
 task_registry.register("h1", H1Robot,H1RoughCfg(), H1RoughCfgPPO())
 task_registry.register("h1_2", H1_2Robot, H1_2RoughCfg(), H1_2RoughCfgPPO())

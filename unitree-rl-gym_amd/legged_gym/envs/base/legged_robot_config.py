@@ -18,6 +18,10 @@ class LeggedRobotCfg(BaseConfig):
         # range.  num_privileged_obs is then the layout's privileged head (the quadruped's clean
         # frame, 12 + 3 A; the humanoid's 14 + 3 A) + the tail + the scan's points.  False: off.
         privileged_parameters = False
+        # privileged_as_observations (envs/base/privileged_actor.py): the env presents
+        # its privileged row as THE observation and no privileged row (a teacher task: actor and
+        # critic share the clean row).  False: off.
+        privileged_as_observations = False
         num_actions = 12
         env_spacing = 3.0          # plane grid spacing [m]
         send_timeouts = True       # extras["time_outs"] for value bootstrapping

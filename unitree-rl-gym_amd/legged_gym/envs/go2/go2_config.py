@@ -119,6 +119,21 @@ class GO2TerrainRobustAsymCfg(GO2TerrainRobustCfg):
         num_privileged_obs = 274
 
 
+class GO2RobustTeacherCfg(GO2RobustAsymCfg):
+    """go2_robust_teacher: go2_robust_asym's env presenting its privileged row (87) as the one
+    observation row: the teacher of go2_robust_distill."""
+
+    class env(GO2RobustAsymCfg.env):
+        privileged_as_observations = True
+
+
+class GO2TerrainRobustTeacherCfg(GO2TerrainRobustAsymCfg):
+    """go2_terrain_robust_teacher: likewise on the terrain task (274 inputs)."""
+
+    class env(GO2TerrainRobustAsymCfg.env):
+        privileged_as_observations = True
+
+
 class GO2RoughCfgPPO(LeggedRobotCfgPPO):
     class algorithm(LeggedRobotCfgPPO.algorithm):
         entropy_coef = 0.01
@@ -179,3 +194,58 @@ class GO2TerrainRobustSymCfgPPO(GO2TerrainRobustAsymCfgPPO):
 
     class runner(GO2TerrainRobustAsymCfgPPO.runner):
         experiment_name = "go2_terrain_robust_sym"
+
+
+class GO2RobustTeacherCfgPPO(GO2RobustAsymCfgPPO):
+    """go2_robust_teacher: PPO as go2_robust_asym's, on the privileged row."""
+
+    class runner(GO2RobustAsymCfgPPO.runner):
+        experiment_name = "go2_robust_teacher"
+
+
+class GO2TerrainRobustTeacherCfgPPO(GO2TerrainRobustAsymCfgPPO):
+    class runner(GO2TerrainRobustAsymCfgPPO.runner):
+        experiment_name = "go2_terrain_robust_teacher"
+
+
+class GO2RobustDistillCfgPPO(LeggedRobotCfgPPO):
+    """go2_robust_distill: the student of go2_robust_teacher on go2_robust_asym's
+    env: the student reads the 240 noisy inputs, the frozen teacher the privileged row (87).  One
+    optimizer step is 6 x 4096 = 24,576 rows, the mini-batch the GEMM tiles were tuned at."""
+
+    class policy:
+        init_noise_std = 0.1
+        student_hidden_dims = [512, 256, 128]
+        teacher_hidden_dims = [512, 256, 128]
+        activation = "elu"
+
+    class algorithm:
+        num_learning_epochs = 1
+        gradient_length = 6
+        learning_rate = 1.0e-3
+        max_grad_norm = None
+        loss_type = "mse"
+
+        # (every train cfg carries the key; Distillation refuses it switched on)
+        class symmetry_cfg(LeggedRobotCfgPPO.algorithm.symmetry_cfg):
+            pass
+
+    class runner(LeggedRobotCfgPPO.runner):
+        policy_class_name = "StudentTeacher"
+        algorithm_class_name = "Distillation"
+        experiment_name = "go2_robust_distill"
+        # the distillation rollout consumes no deferred env extras: the env keeps its own launch
+        defer_env_extras = False
+        # the teacher's checkpoint: logs/<teacher_experiment_name>/<teacher_load_run>/model_<n>.pt
+        # (-1: the last run / the last checkpoint, as load_run / checkpoint)
+        teacher_experiment_name = "go2_robust_teacher"
+        teacher_load_run = -1
+        teacher_checkpoint = -1
+
+
+class GO2TerrainRobustDistillCfgPPO(GO2RobustDistillCfgPPO):
+    """go2_terrain_robust_distill: 427 student inputs, 274 teacher inputs."""
+
+    class runner(GO2RobustDistillCfgPPO.runner):
+        experiment_name = "go2_terrain_robust_distill"
+        teacher_experiment_name = "go2_terrain_robust_teacher"

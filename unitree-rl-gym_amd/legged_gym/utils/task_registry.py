@@ -76,6 +76,15 @@ class TaskRegistry:
         else:
             log_dir = os.path.join(log_root, stamp)
         runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir, device=args.rl_device)
+        teacher_name = getattr(train_cfg.runner, "teacher_experiment_name", None)
+        if teacher_name and train_cfg.runner.algorithm_class_name == "Distillation" and not train_cfg.runner.resume:
+            # distillation: the frozen teacher comes from the teacher task's run (a
+            # resumed run, play.py included, takes it from its own checkpoint's teacher.*)
+            teacher_root = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", teacher_name)
+            teacher_path = get_load_path(teacher_root, load_run=getattr(train_cfg.runner, "teacher_load_run", -1),
+                                         checkpoint=getattr(train_cfg.runner, "teacher_checkpoint", -1))
+            print(f"Loading teacher from: {teacher_path}")
+            runner.load_teacher(teacher_path)
         if train_cfg.runner.resume:
             resume_path = get_load_path(log_root, load_run=train_cfg.runner.load_run,
                                         checkpoint=train_cfg.runner.checkpoint)

@@ -50,6 +50,17 @@ def _ceil8(n):
     return (n + 7) // 8 * 8
 
 
+def _first_layer_pads(widths):
+    """mm._pad_k0_nets, except for nets of one width whose fp32 rows are no multiple of 4 floats
+    and whose padding to 8 is no multiple of 16 (87 for actor and critic alike: a teacher task,
+    DESIGN 3.20).  The per-layer GEMMs refuse such rows and the one-launch forward takes multiples
+    of 16, so these pad to 16 (87 -> 96); every width the per-layer path takes keeps its padding."""
+    pads = mm._pad_k0_nets(widths)
+    if any(n % 4 and k % 16 for n, k in zip(widths, pads)):
+        pads = [(k + 15) // 16 * 16 for k in pads]
+    return pads
+
+
 class FusedPPOStep:
     def __init__(self, alg, mini_batch_size):
         ac = alg.actor_critic
@@ -111,7 +122,7 @@ class FusedPPOStep:
         M, dev, bf = self.M, self.dev, torch.bfloat16
         L = len(self.lins[0])
         self.L = L
-        self.k0p = mm._pad_k0_nets([ls[0].in_features for ls in self.lins])
+        self.k0p = _first_layer_pads([ls[0].in_features for ls in self.lins])
         # row-major activations of exactly the layer's width (rows of 512 / 256 / 128 features
         # start on 128-byte lines); the weight gradients read them through LDS-transposed MFMA
         # operands (PARTIAL_TN: no transposed copy is ever written) and form the bias gradient

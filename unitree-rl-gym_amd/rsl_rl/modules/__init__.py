@@ -1,2 +1,3 @@
 from .actor_critic import ActorCritic
 from .actor_critic_recurrent import ActorCriticRecurrent
+from .student_teacher import StudentTeacher

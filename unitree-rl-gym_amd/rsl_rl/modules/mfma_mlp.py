@@ -194,6 +194,10 @@ def load():
         L.pmlp_obs_norm_scratch_bytes.restype = i64
         L.pmlp_obs_norm_step.argtypes = [i32, C.POINTER(ObsNormJob), i32, i32, i64, C.c_double, vp]
         L.pmlp_mirror_rows.argtypes = [i32, C.POINTER(MirrorRowsJob), i64, vp]
+        L.pmlp_distill_act.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, C.c_uint64, vp, vp, vp, vp]
+        L.pmlp_distill_loss_parts.argtypes = [i32]
+        L.pmlp_distill_loss_parts.restype = i32
+        L.pmlp_distill_loss_step.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
         _lib = L
     return _lib
 
@@ -399,6 +403,30 @@ def mirror_rows(jobs, R):
                              None if tab is None else _p(tab.sign), None if tab is None else tab.perm_host)
     arr = (MirrorRowsJob * len(jobs))(*[mk(j) for j in jobs])
     _ok(load().pmlp_mirror_rows(len(jobs), arr, int(R), _stream()), "pmlp_mirror_rows")
+
+
+DISTILL_LOSS = {"mse": 0, "huber": 1}  # include/ppo_mlp.h PMLP_DISTILL_MSE / PMLP_DISTILL_HUBER
+DISTILL_ACT_MAX_A, DISTILL_LOSS_MAX_A = 16, 32
+
+
+def distill_act(mu, mu_t, std, obs, draw, parity, seed, actions_out, st_obs, st_teacher_actions):
+    """pmlp_distill_act: the student's sampled actions (pmlp_act's bits) from mu [N, A] and std [A],
+    the storage rows st_obs = obs and st_teacher_actions = mu_t, and draw[parity ^ 1] =
+    draw[parity] + 1 (draw: int64 [2]); one launch."""
+    N, A = mu.shape
+    _ok(load().pmlp_distill_act(_p(mu), _p(mu_t), _p(std), _p(obs), N, A, obs.shape[1], _p(draw), int(parity),
+                                int(seed), _p(actions_out), _p(st_obs), _p(st_teacher_actions), _stream()),
+        "pmlp_distill_act")
+
+
+def distill_loss_step(mu, target, loss_type, scale, partial, stats, dmu_b, dmu_f=None):
+    """pmlp_distill_loss_step: the behaviour loss of one optimizer step on mu, target [M, A] (fp32
+    rows): the gradient into dmu_b (bf16 [M, Ap], padded columns zero; dmu_f fp32 [M, A] optional),
+    one partial per 64 rows and stats[0] = the step's loss (stats[1:4] = 0)."""
+    M, A = mu.shape
+    _ok(load().pmlp_distill_loss_step(_p(mu), _p(target), M, A, DISTILL_LOSS[loss_type], float(scale), _p(partial),
+                                      _p(stats), _p(dmu_b), _p(dmu_f), dmu_b.shape[1], _stream()),
+        "pmlp_distill_loss_step")
 
 
 def permutation_(out):

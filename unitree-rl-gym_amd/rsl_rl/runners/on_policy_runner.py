@@ -10,9 +10,9 @@ from collections import deque
 import torch
 import torch.distributed as dist
 
-from rsl_rl.algorithms import PPO  # noqa: F401  (eval'd by name)
+from rsl_rl.algorithms import PPO, Distillation  # noqa: F401  (eval'd by name)
 from rsl_rl.env import VecEnv
-from rsl_rl.modules import ActorCritic, ActorCriticRecurrent  # noqa: F401  (eval'd by name)
+from rsl_rl.modules import ActorCritic, ActorCriticRecurrent, StudentTeacher  # noqa: F401  (eval'd by name)
 from rsl_rl.modules.normalizer import EmpiricalNormalization, normalize_pair
 from rsl_rl.utils import capture_without_gc
 
@@ -124,6 +124,10 @@ class OnPolicyRunner:
         self.device = device
         self.env = env
         num_critic_obs = self.env.num_privileged_obs if self.env.num_privileged_obs is not None else self.env.num_obs
+        # teacher-student distillation: the privileged row is the teacher's input
+        self.distillation = self.cfg["algorithm_class_name"] == "Distillation"
+        if self.distillation:
+            self._check_distillation()
         actor_critic_class = eval(self.cfg["policy_class_name"])
         actor_critic = actor_critic_class(self.env.num_obs, num_critic_obs, self.env.num_actions,
                                           **self.policy_cfg).to(self.device)
@@ -213,7 +217,9 @@ class OnPolicyRunner:
                 collection_time = stop - start
                 start = stop
                 self.alg.compute_returns(critic_obs)
-            if self.log_dir is not None or exact:
+            if self.distillation:
+                mean_behavior_loss = self.alg.update(host_means=self.log_dir is not None or exact)  # noqa: F841
+            elif self.log_dir is not None or exact:
                 mean_value_loss, mean_surrogate_loss = self.alg.update()
             else:  # nothing reads the losses: no read-back, the host stays ahead of the device
                 mean_value_loss, mean_surrogate_loss = self.alg.update(host_means=False)
@@ -277,6 +283,33 @@ class OnPolicyRunner:
             obs, critic_obs = normalize_pair(self.obs_normalizer, obs, self.critic_obs_normalizer, critic_obs)
         self.alg.process_env_step(rewards, dones, infos)
         return obs, critic_obs, rewards, dones, infos
+
+    def _check_distillation(self):
+        """What Distillation does not take, refused before anything is built."""
+        if self.cfg["policy_class_name"] != "StudentTeacher":
+            raise ValueError(f"Distillation needs policy_class_name 'StudentTeacher', not "
+                             f"{self.cfg['policy_class_name']!r} (a recurrent student or teacher is not supported)")
+        if self.cfg.get("empirical_normalization", False):
+            raise ValueError("Distillation with empirical_normalization is not supported: the teacher was trained "
+                             "on its own statistics, which a student run does not carry")
+        sym = self.alg_cfg.get("symmetry_cfg") or {}
+        if sym.get("use_data_augmentation", False) or sym.get("use_mirror_loss", False):
+            raise ValueError("Distillation does not support symmetry_cfg (the mirrored rows belong to PPO's update)")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("Distillation is single-process: a torch.distributed world size above 1 is not supported")
+
+    def load_teacher(self, path):
+        """The teacher's parameters from a PPO checkpoint of the teacher task (its `actor.*`), or
+        from a distillation checkpoint (its `teacher.*`); the student, the optimizer and the
+        iteration count are left alone."""
+        if not self.distillation:
+            raise ValueError("load_teacher: the algorithm is not Distillation")
+        loaded = torch.load(path, map_location=self.device, weights_only=True)
+        sd = loaded["model_state_dict"]
+        if any(k.startswith("student.") for k in sd):  # a distillation run's teacher
+            sd = {"actor." + k[len("teacher."):]: v for k, v in sd.items() if k.startswith("teacher.")}
+        self.alg.actor_critic.load_state_dict(sd)
+        self.alg.teacher_loaded()
 
     def _build_normalizers(self, actor_critic, num_critic_obs):
         """Runner cfg `empirical_normalization`: EmpiricalNormalization modules registered on the
@@ -359,8 +392,11 @@ class OnPolicyRunner:
                 ep_string += f"""{f'Mean episode {key}:':>{pad}} {value:.4f}\n"""
         mean_std = self.alg.actor_critic.std.mean()
         fps = int(self.num_steps_per_env * self.env.num_envs * ws / iteration_time)
-        self.writer.add_scalar("Loss/value_function", locs["mean_value_loss"], it)
-        self.writer.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
+        if self.distillation:
+            self.writer.add_scalar("Loss/behavior", locs["mean_behavior_loss"], it)
+        else:
+            self.writer.add_scalar("Loss/value_function", locs["mean_value_loss"], it)
+            self.writer.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
         self.writer.add_scalar("Loss/learning_rate", self.alg.learning_rate, it)
         self.writer.add_scalar("Policy/mean_noise_std", mean_std.item(), it)
         self.writer.add_scalar("Perf/total_fps", fps, it)
@@ -375,8 +411,9 @@ class OnPolicyRunner:
         lines = [
             "#" * width, head.center(width, " "), "",
             f"""{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)""",
-            f"""{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}""",
-            f"""{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}""",
+        ] + ([f"""{'Behavior loss:':>{pad}} {locs['mean_behavior_loss']:.4f}"""] if self.distillation else
+             [f"""{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}""",
+              f"""{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}"""]) + [
             f"""{'Mean action noise std:':>{pad}} {mean_std.item():.2f}""",
         ]
         if len(locs["rewbuffer"]) > 0:
@@ -397,9 +434,13 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         loaded = torch.load(path, map_location=self.device, weights_only=True)
-        self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
+        resumed = self.alg.actor_critic.load_state_dict(loaded["model_state_dict"])
         if getattr(self.alg, "_fused", None) is not None:  # bf16 weight copies of the native rollout
             self.alg._fused.weights_changed = True
+        if self.distillation:
+            self.alg.teacher_loaded()
+            if resumed is False:  # a PPO checkpoint filled the teacher: not a resume (StudentTeacher's rule)
+                return loaded["infos"]
         if load_optimizer:
             self.alg.optimizer.load_state_dict(loaded["optimizer_state_dict"])
             # a captured autograd update reads the previous Adam state tensors: recapture

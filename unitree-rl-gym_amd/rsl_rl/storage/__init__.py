@@ -1,1 +1,2 @@
 from .rollout_storage import RolloutStorage
+from .distillation_storage import DistillationStorage
