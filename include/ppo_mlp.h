@@ -735,4 +735,38 @@ PMLP_API int pmlp_distill_loss_step(const float* mu, const float* target, int32_
                                     float scale, float* partial, float* stats, void* dmu_b, float* dmu_f, int32_t Ap,
                                     void* stream);
 
+/* ---- random network distillation (rsl_rl 2.x RandomNetworkDistillation; csrc/rnd.hip):
+ * the two scalar kernels around the library's GEMMs.
+ *
+ * pmlp_rnd_reward: the exploration bonus of a finished rollout, after one pmlp_mlp_forward of two
+ * jobs over the M = T * N flat storage rows has written pred[M,E] (the predictor) and tgt[M,E] (the
+ * frozen target).  Per row m, storage step t = m / N:
+ *   r = sqrt(sum_k d_k^2), d = tgt - pred, summed in k order, every product and sum one rounding
+ *   bonus = w[t] * r;  rewards[m] += bonus (in place);  intrinsic[m] = bonus (optional, may be NULL)
+ *   partial[2 * pmlp_rnd_parts(M)]  per 64 rows the sum of the bonuses, then (from index
+ *                       pmlp_rnd_parts(M)) the sum of the r's, each by a fixed butterfly
+ *   stats[2]            [mean bonus, mean r]: the partials summed in a fixed order, times
+ *                       float(1) / float(M)
+ * No atomics: two launches on equal inputs give equal bits.  E <= PMLP_RND_MAX_E; E % 4 == 0 with
+ * 16-byte aligned pred and tgt loads 16 bytes at a time, any other E by element (the same bits).
+ * Two launches (the rows, then a one-wave finish).  Errors: -1 bad argument, -3 E too large, -4
+ * more than 2^30 rows, -2 a launch failed.
+ *
+ * pmlp_rnd_loss_step: the predictor's loss of one mini-batch, forward and backward.  mu[M,A] is the
+ * predictor on the gathered rows, tgt_all[R,A] the stored targets of the whole rollout and
+ * idx[M] (int64, 0 .. R-1) the mini-batch's rows: d = mu[i] - tgt_all[idx[i]], and from there
+ * pmlp_distill_loss_step's PMLP_DISTILL_MSE arm, operation for operation (gradient (2 d) * scale
+ * into dmu_b[M,Ap] in bf16 with zero padding and optionally dmu_f[M,A], one partial per 64 rows,
+ * stats[4] = [sum * scale, 0, 0, 0]): with idx the identity and R = M the outputs are that entry
+ * point's bit for bit.  An index outside 0 .. R-1 reads nothing; its row contributes zeros.  The
+ * same limits (A <= PMLP_RND_MAX_E, Ap a multiple of 8 in A .. PMLP_RND_MAX_E, dmu_b 16-byte
+ * aligned) and error codes (-1, -3, -4, -5, -2).                                                */
+#define PMLP_RND_MAX_E 32
+PMLP_API int32_t pmlp_rnd_parts(int64_t M);
+PMLP_API int pmlp_rnd_reward(const float* pred, const float* tgt, const float* w, int32_t T, int32_t N, int32_t E,
+                             float* rewards, float* intrinsic, float* partial, float* stats, void* stream);
+PMLP_API int pmlp_rnd_loss_step(const float* mu, const float* tgt_all, const int64_t* idx, int32_t M, int32_t R,
+                                int32_t A, float scale, float* partial, float* stats, void* dmu_b, float* dmu_f,
+                                int32_t Ap, void* stream);
+
 #endif

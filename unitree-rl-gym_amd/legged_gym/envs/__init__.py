@@ -1,6 +1,7 @@
 """Task registration (reference envs/__init__.py:1-27): the plugin API."""
 from legged_gym import LEGGED_GYM_ROOT_DIR, LEGGED_GYM_ENVS_DIR  # noqa: F401
 
+from legged_gym.envs.go2.go2_config import GO2RobustRndCfgPPO, GO2TerrainRobustRndCfgPPO
 from legged_gym.envs.go2.go2_config import (GO2RobustDistillCfgPPO, GO2RobustTeacherCfg, GO2RobustTeacherCfgPPO,
                                             GO2TerrainRobustDistillCfgPPO, GO2TerrainRobustTeacherCfg,
                                             GO2TerrainRobustTeacherCfgPPO)
@@ -32,6 +33,8 @@ task_registry.register("go2_robust_asym", LeggedRobot, GO2RobustAsymCfg(), GO2Ro
 task_registry.register("go2_terrain_robust_asym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustAsymCfgPPO())
 task_registry.register("go2_robust_sym", LeggedRobot, GO2RobustAsymCfg(), GO2RobustSymCfgPPO())
 task_registry.register("go2_terrain_robust_sym", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustSymCfgPPO())
+task_registry.register("go2_robust_rnd", LeggedRobot, GO2RobustAsymCfg(), GO2RobustRndCfgPPO())
+task_registry.register("go2_terrain_robust_rnd", LeggedRobot, GO2TerrainRobustAsymCfg(), GO2TerrainRobustRndCfgPPO())
 task_registry.register("go2_robust_teacher", PrivilegedActorRobot, GO2RobustTeacherCfg(), GO2RobustTeacherCfgPPO())
 task_registry.register("go2_terrain_robust_teacher", PrivilegedActorRobot, GO2TerrainRobustTeacherCfg(),
                        GO2TerrainRobustTeacherCfgPPO())

@@ -244,6 +244,21 @@ class LeggedRobotCfgPPO(BaseConfig):
             use_mirror_loss = False
             mirror_loss_coeff = 0.0
 
+        # random network distillation (rsl_rl 2.x's names): an exploration bonus
+        # weight * ||target(s) - predictor(s)||_2 added to the rewards of every rollout.  weight 0
+        # with no schedule: off.  state: the stored row the nets read, "critic" (the privileged
+        # row where there is one) or "policy".  The two normalisers are refused (not built yet).
+        class rnd_cfg:
+            weight = 0.0
+            weight_schedule = None
+            learning_rate = 1.0e-3
+            num_outputs = 16
+            predictor_hidden_dims = [256, 128, 64]
+            target_hidden_dims = [256, 128, 64]
+            reward_normalization = False
+            state_normalization = False
+            state = "critic"
+
     class runner:
         policy_class_name = "ActorCritic"
         algorithm_class_name = "PPO"

@@ -196,6 +196,36 @@ class GO2TerrainRobustSymCfgPPO(GO2TerrainRobustAsymCfgPPO):
         experiment_name = "go2_terrain_robust_sym"
 
 
+class GO2RobustRndCfgPPO(GO2RobustAsymCfgPPO):
+    """go2_robust_rnd: go2_robust_asym with random network distillation on the
+    privileged row (87).  The weight is a starting point, not a tuned value: see DESIGN 3.21 for
+    the measurement it comes from.  It decays linearly to 0 over the first half of the run (the
+    schedule counts env steps: max_iterations / 2 x num_steps_per_env)."""
+
+    class algorithm(GO2RobustAsymCfgPPO.algorithm):
+        class rnd_cfg(GO2RobustAsymCfgPPO.algorithm.rnd_cfg):
+            weight = 1.4e-5
+            weight_schedule = {"mode": "linear", "initial_step": 0, "final_step": 750 * 24, "final_value": 0.0}
+            state = "critic"
+
+    class runner(GO2RobustAsymCfgPPO.runner):
+        experiment_name = "go2_robust_rnd"
+
+
+class GO2TerrainRobustRndCfgPPO(GO2TerrainRobustAsymCfgPPO):
+    """go2_terrain_robust_rnd: go2_terrain_robust_asym with random network distillation on the
+    privileged row (274)."""
+
+    class algorithm(GO2TerrainRobustAsymCfgPPO.algorithm):
+        class rnd_cfg(GO2TerrainRobustAsymCfgPPO.algorithm.rnd_cfg):
+            weight = 1.5e-5
+            weight_schedule = {"mode": "linear", "initial_step": 0, "final_step": 750 * 24, "final_value": 0.0}
+            state = "critic"
+
+    class runner(GO2TerrainRobustAsymCfgPPO.runner):
+        experiment_name = "go2_terrain_robust_rnd"
+
+
 class GO2RobustTeacherCfgPPO(GO2RobustAsymCfgPPO):
     """go2_robust_teacher: PPO as go2_robust_asym's, on the privileged row."""
 

@@ -19,9 +19,10 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.optim as optim
 
-from rsl_rl.algorithms import fused_recurrent, fused_step
+from rsl_rl.algorithms import fused_recurrent, fused_step, rnd_step
 from rsl_rl.modules import ActorCritic
 from rsl_rl.modules import gru_seq, mfma_mlp
+from rsl_rl.modules.rnd import RandomNetworkDistillation, parse_cfg as parse_rnd_cfg
 from rsl_rl.storage import RolloutStorage
 from rsl_rl.storage.rollout_storage import minibatch_permutation
 from rsl_rl.utils import capture_without_gc
@@ -39,13 +40,19 @@ class PPO:
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", fused_loss=True,
-                 symmetry_cfg=None, symmetry_tables=None):
+                 symmetry_cfg=None, symmetry_tables=None, rnd_cfg=None):
         """symmetry_cfg (rsl_rl 2.x's keys use_data_augmentation, use_mirror_loss, mirror_loss_coeff;
         None: off) with symmetry_tables, the env's (policy row, critic row, action row) signed
         permutations (LeggedRobot.symmetry_tables(); OnPolicyRunner passes them): every mini-batch
-        is trained together with its mirror image."""
+        is trained together with its mirror image.
+
+        rnd_cfg (rsl_rl 2.x's keys and `state`; None or weight 0 without a schedule: off): random
+        network distillation.  The bonus of every storage row is added to the rewards
+        once per iteration, between the rollout and GAE; the predictor is stepped by its own Adam
+        after every mini-batch's PPO step."""
         self.device = device
         self._sym = self._symmetry(actor_critic, symmetry_cfg, symmetry_tables)
+        self._rnd_cfg = self._rnd_refusals(actor_critic, rnd_cfg)
         self.desired_kl = desired_kl
         self.schedule = schedule
         self.actor_critic = actor_critic
@@ -110,6 +117,14 @@ class PPO:
         self._graph_calls = 0
         self._capturing = False
         self._gflat = None  # world > 1: the gradient bucket (_grad_bucket)
+        # random network distillation: the nets and the predictor's Adam are built with the storage
+        # (init_storage: the state row's width is known there)
+        self.rnd = self.rnd_optimizer = self._rnd_lr = None
+        self._rnd_fused = self._rnd_pass = None  # FusedRndStep, RndRewardPass
+        self._rnd_acc = None  # [0, sum of the update's per-step RND losses]
+        self._rnd_stats = None  # [mean bonus, mean error] of the last reward pass
+        self.rnd_loss_mean = None  # device scalar: the last update's mean RND loss
+        self.rnd_iteration = 0  # rollouts the schedule's counter has passed
         if self.world_size > 1:
             for p in params:  # identical initial policy on every rank
                 dist.broadcast(p.data, src=0)
@@ -137,6 +152,111 @@ class PPO:
         if len(tables) != 3:
             raise ValueError("symmetry_tables: (policy row, critic row, action row) tables")
         return tuple(mfma_mlp.SignedPermutation(p, sg, self.device) for p, sg in tables)
+
+    def _rnd_refusals(self, actor_critic, cfg):
+        """The checked rnd_cfg, or None when RND is off; the refusals of DESIGN 3.21."""
+        cfg = parse_rnd_cfg(cfg)
+        if cfg is None:
+            return None
+        if getattr(actor_critic, "is_recurrent", False):
+            raise ValueError("rnd_cfg is not supported for recurrent policies (the recurrent update has no gathered "
+                             "mini-batch rows for the predictor's step)")
+        if self._sym is not None:
+            raise ValueError("rnd_cfg with symmetry_cfg.use_data_augmentation is not supported (the predictor would "
+                             "need the mirrored state rows and targets)")
+        if _dist_world() > 1:
+            raise ValueError("rnd_cfg is single-process: a torch.distributed world size above 1 needs an all-reduce "
+                             "of the predictor's gradient")
+        return cfg
+
+    def _init_rnd(self, num_envs, T, actor_obs_shape, critic_obs_shape):
+        cfg = self._rnd_cfg
+        priv = critic_obs_shape[0] is not None
+        self._rnd_state_name = "privileged_observations" if cfg["state"] == "critic" and priv else "observations"
+        width = critic_obs_shape[0] if self._rnd_state_name == "privileged_observations" else actor_obs_shape[0]
+        if self.rnd is None:
+            self.rnd = RandomNetworkDistillation(width, cfg, self.device)
+            self._rnd_lr = torch.tensor(cfg["learning_rate"], device=self.device)
+            params = list(self.rnd.predictor.parameters())
+            if str(self.device).startswith("cuda"):
+                for kw in (dict(fused=True, capturable=True), dict(foreach=True, capturable=True)):
+                    try:
+                        self.rnd_optimizer = optim.Adam(params, lr=self._rnd_lr, **kw)
+                        break
+                    except (RuntimeError, TypeError, ValueError):
+                        continue
+            if self.rnd_optimizer is None:
+                self.rnd_optimizer = optim.Adam(params, lr=cfg["learning_rate"])
+        elif self.rnd.num_states != width:
+            raise ValueError(f"rnd: nets of {self.rnd.num_states} inputs for state rows of {width}")
+        self._rnd_acc = torch.zeros(2, device=self.device)
+        self._rnd_stats = torch.zeros(2, device=self.device)
+        self.rnd_loss_mean = torch.zeros((), device=self.device)
+        self._rnd_fused = self._rnd_pass = None
+        if self._fused is not None:
+            # the fused pieces (algorithms/rnd_step.py).  Whether they take the nets is decided before
+            # anything is built: building the step re-points the predictor and its optimizer's state
+            # at flat buffers, which the plain path must never inherit.
+            mb = num_envs * T // self.num_mini_batches
+            why = None if self.rnd_optimizer.defaults.get("capturable", False) else \
+                "the predictor's Adam is not capturable on this torch"
+            why = why or rnd_step.supported(self.rnd, mb)
+            if why is None:
+                self._rnd_fused = rnd_step.FusedRndStep(self.rnd, self.rnd_optimizer, self._rnd_lr, mb)
+                self._rnd_pass = rnd_step.RndRewardPass(self._rnd_fused, T, num_envs)
+            else:  # not an error, but not silent either: the hot path is lost
+                warnings.warn(f"PPO: random network distillation runs on the plain fp32 path beside the fused PPO "
+                              f"update ({why})")
+
+    def _rnd_states(self):
+        """The flat [T N, S] state rows RND reads: the storage's own (already normalised) rows."""
+        return getattr(self.storage, self._rnd_state_name).flatten(0, 1)
+
+    def rnd_loaded(self):
+        """After rnd.load_state_dict / rnd_optimizer.load_state_dict: the bf16 copies of both nets
+        lag the weights, and the flat Adam moments the loaded state."""
+        if self._rnd_fused is not None:
+            self._rnd_fused.weights_changed = True
+            self._rnd_pass.target_changed = True
+            self._rnd_fused.sync_optimizer_state(self.rnd_optimizer)
+
+    def _rnd_rewards(self):
+        """rewards[t, n] += w_t ||target(s) - predictor(s)||_2 for every storage row, once per
+        iteration (after the rollout is flushed, before GAE); the time-out bootstrap is already in
+        the rewards.  w_t: the schedule at counter iteration x T + t."""
+        st = self.storage
+        T, N = st.num_transitions_per_env, st.num_envs
+        base = self.rnd_iteration * T
+        weights = [self.rnd.weight_at(base + t) for t in range(T)]
+        self.rnd_iteration += 1
+        self.rnd.update_counter = base + T
+        states = self._rnd_states()
+        if self._rnd_pass is not None:
+            self._rnd_pass.set_weights(weights)
+            self._rnd_pass.run(states, st.rewards)
+            self._rnd_stats = self._rnd_pass.stats
+            return
+        r = self.rnd.error(states)
+        w = torch.tensor(weights, dtype=torch.float32, device=r.device).repeat_interleave(N)
+        bonus = w * r
+        st.rewards += bonus.view(T, N, 1)
+        self._rnd_stats = torch.stack([bonus.mean(), r.mean()])
+
+    def _rnd_minibatch_step(self, state_batch):
+        """The predictor's optimizer step on a mini-batch's state rows (the plain path): the mean
+        over mb x E entries of (predictor - target)^2, its own Adam, no clipping; nothing flows
+        into the policy."""
+        with torch.enable_grad():
+            with torch.no_grad():
+                tgt = self.rnd.target(state_batch)
+            loss = torch.nn.functional.mse_loss(self.rnd.predictor(state_batch.detach()), tgt)
+            self.rnd_optimizer.zero_grad()
+            loss.backward()
+        self.rnd_optimizer.step()
+        with torch.no_grad():
+            self._rnd_acc[1] += loss.detach()
+        if self._rnd_fused is not None:  # (a caller that ran this next to the fused step)
+            self._rnd_fused.weights_changed = True
 
     def _augment(self, obs, cobs, actions, values, adv, ret, logp, mu, sigma):
         """A mini-batch followed by its mirror image, in torch: observations, actions and the old
@@ -188,6 +308,8 @@ class PPO:
         if self.actor_critic.is_recurrent and self._rollout is None and str(self.device).startswith("cuda") and \
                 hasattr(self.actor_critic, "rollout_capturable"):
             self._rollout = fused_step.RecurrentRollout(self, num_envs)
+        if self._rnd_cfg is not None:
+            self._init_rnd(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape)
 
     def test_mode(self):
         self.actor_critic.eval()
@@ -274,6 +396,8 @@ class PPO:
 
     def compute_returns(self, last_critic_obs):
         self.flush_rollout()
+        if self.rnd is not None:
+            self._rnd_rewards()
         last_values = None
         if isinstance(self._rollout, fused_step.FusedRollout):  # one launch instead of the layer GEMMs
             last_values = self._rollout.values(last_critic_obs)
@@ -483,10 +607,13 @@ class PPO:
             acc = self._update_fused()
         elif self._rfused is not None:
             acc = self._update_rfused()
-        elif self.use_graph and self._graph_calls >= 2:  # first call runs eagerly (warm-up)
-            acc = self._update_graphed()
+        elif self.use_graph and self._graph_calls >= 2 and self.rnd is None:  # first call runs eagerly (warm-up)
+            acc = self._update_graphed()  # (with RND's plain path the update stays eager)
         else:
             acc = torch.zeros(2, device=self.device)
+            if self.rnd is not None:
+                self._rnd_acc.zero_()
+                rnd_col = 1 if self._rnd_state_name == "privileged_observations" else 0
             if self.actor_critic.is_recurrent and self._dense_recurrent:
                 gen = self.storage.recurrent_dense_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
             elif self.actor_critic.is_recurrent:
@@ -495,7 +622,11 @@ class PPO:
                 gen = self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
             for batch in gen:
                 self._minibatch_step(*batch, acc)
+                if self.rnd is not None:
+                    self._rnd_minibatch_step(batch[rnd_col])
         means = acc / num_updates
+        if self.rnd is not None:
+            self.rnd_loss_mean = self._rnd_acc[1] / num_updates
         self.storage.clear()
         if not host_means:
             return means
@@ -509,6 +640,10 @@ class PPO:
         f, st = self._fused, self.storage
         f.sync_optimizer_state(self.optimizer)
         f.ensure_weights()  # the captured steps read the bf16 weight copies from the first one
+        rf = self._rnd_fused
+        if rf is not None:
+            rf.sync_optimizer_state(self.rnd_optimizer)
+            rf.ensure_weights()
         sym = self._sym is not None
         mb = f.M // 2 if sym else f.M
         nmb = self.num_mini_batches
@@ -545,13 +680,29 @@ class PPO:
             if sym:  # GAE and the normalisation have written the first half: now its mirror image
                 mfma_mlp.mirror_rows(self._fmirror, nmb * mb)
             self._facc.zero_()
+            if rf is not None:
+                self._rnd_acc.zero_()
             for _ in range(self.num_learning_epochs):
                 for i in range(nmb):
                     rows = self._fidx[i] if sym else self._fperm[i * mb:(i + 1) * mb]
                     f.run(rows, self._fsrc, self._facc)
+                    if rf is not None:  # the predictor's step on the same rows, in the same graph
+                        rf.run(rows, self._fsrc[rnd_col], self._rnd_pass.tgt_all, self._rnd_acc)
 
+        def rnd_plain():
+            # RND nets the fused pieces do not take: the plain steps on the same rows, after the
+            # (captured) PPO steps -- nothing flows between the two, so the order is free
+            if self.rnd is None or rf is not None:
+                return
+            self._rnd_acc.zero_()
+            for _ in range(self.num_learning_epochs):
+                for i in range(nmb):
+                    self._rnd_minibatch_step(self._fsrc[rnd_col].index_select(0, self._fperm[i * mb:(i + 1) * mb]))
+
+        rnd_col = 1 if self.rnd is not None and self._rnd_state_name == "privileged_observations" else 0
         if not (self.use_graph and self._graph_calls >= 2):
             body()
+            rnd_plain()
             return self._facc
         if self._fgraph is None:
             side = torch.cuda.Stream(self.device)
@@ -559,10 +710,12 @@ class PPO:
             graph = torch.cuda.CUDAGraph()
             if not self._capture(graph, side, body):
                 body()
+                rnd_plain()
                 return self._facc
             torch.cuda.current_stream(self.device).wait_stream(side)
             self._fgraph = graph
         self._fgraph.replay()
+        rnd_plain()
         return self._facc
 
     def _update_rfused(self):

@@ -198,6 +198,10 @@ def load():
         L.pmlp_distill_loss_parts.argtypes = [i32]
         L.pmlp_distill_loss_parts.restype = i32
         L.pmlp_distill_loss_step.argtypes = [vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
+        L.pmlp_rnd_parts.argtypes = [i64]
+        L.pmlp_rnd_parts.restype = i32
+        L.pmlp_rnd_reward.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.pmlp_rnd_loss_step.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
         _lib = L
     return _lib
 
@@ -427,6 +431,26 @@ def distill_loss_step(mu, target, loss_type, scale, partial, stats, dmu_b, dmu_f
     _ok(load().pmlp_distill_loss_step(_p(mu), _p(target), M, A, DISTILL_LOSS[loss_type], float(scale), _p(partial),
                                       _p(stats), _p(dmu_b), _p(dmu_f), dmu_b.shape[1], _stream()),
         "pmlp_distill_loss_step")
+
+
+RND_MAX_E = 32  # include/ppo_mlp.h PMLP_RND_MAX_E
+
+
+def rnd_reward(pred, tgt, w, T, N, rewards, intrinsic, partial, stats):
+    """pmlp_rnd_reward: rewards[m] += w[m // N] * ||tgt[m] - pred[m]||_2 over the T * N flat rows
+    (pred, tgt fp32 [T N, E]); intrinsic (optional) = the bonus, partial [2 parts], stats =
+    [mean bonus, mean error]."""
+    _ok(load().pmlp_rnd_reward(_p(pred), _p(tgt), _p(w), int(T), int(N), pred.shape[1], _p(rewards), _p(intrinsic),
+                               _p(partial), _p(stats), _stream()), "pmlp_rnd_reward")
+
+
+def rnd_loss_step(mu, tgt_all, idx, scale, partial, stats, dmu_b, dmu_f=None):
+    """pmlp_rnd_loss_step: the predictor's mse against tgt_all[idx] on mu [M, A]: the outputs of
+    distill_loss_step("mse") with the target read through idx (int64 [M])."""
+    M, A = mu.shape
+    _ok(load().pmlp_rnd_loss_step(_p(mu), _p(tgt_all), _p(idx), M, tgt_all.shape[0], A, float(scale), _p(partial),
+                                  _p(stats), _p(dmu_b), _p(dmu_f), dmu_b.shape[1], _stream()),
+        "pmlp_rnd_loss_step")
 
 
 def permutation_(out):

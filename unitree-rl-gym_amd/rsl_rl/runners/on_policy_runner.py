@@ -397,6 +397,16 @@ class OnPolicyRunner:
         else:
             self.writer.add_scalar("Loss/value_function", locs["mean_value_loss"], it)
             self.writer.add_scalar("Loss/surrogate", locs["mean_surrogate_loss"], it)
+        rnd_lines = []
+        if getattr(self.alg, "rnd", None) is not None:
+            # (the bonus is known per rollout, not per step: no per-episode intrinsic returns)
+            bonus, _ = self.alg._rnd_stats.tolist()
+            rnd_loss, weight = float(self.alg.rnd_loss_mean), self.alg.rnd.weight
+            self.writer.add_scalar("Loss/rnd", rnd_loss, it)
+            self.writer.add_scalar("Rnd/mean_intrinsic_reward", bonus, it)
+            self.writer.add_scalar("Rnd/weight", weight, it)
+            rnd_lines = [f"""{'RND loss:':>{pad}} {rnd_loss:.3e}""",
+                         f"""{'Mean intrinsic reward:':>{pad}} {bonus:.3e} (weight {weight:.3e})"""]
         self.writer.add_scalar("Loss/learning_rate", self.alg.learning_rate, it)
         self.writer.add_scalar("Policy/mean_noise_std", mean_std.item(), it)
         self.writer.add_scalar("Perf/total_fps", fps, it)
@@ -413,7 +423,7 @@ class OnPolicyRunner:
             f"""{'Computation:':>{pad}} {fps:.0f} steps/s (collection: {locs['collection_time']:.3f}s, learning {locs['learn_time']:.3f}s)""",
         ] + ([f"""{'Behavior loss:':>{pad}} {locs['mean_behavior_loss']:.4f}"""] if self.distillation else
              [f"""{'Value function loss:':>{pad}} {locs['mean_value_loss']:.4f}""",
-              f"""{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}"""]) + [
+              f"""{'Surrogate loss:':>{pad}} {locs['mean_surrogate_loss']:.4f}"""]) + rnd_lines + [
             f"""{'Mean action noise std:':>{pad}} {mean_std.item():.2f}""",
         ]
         if len(locs["rewbuffer"]) > 0:
@@ -428,9 +438,13 @@ class OnPolicyRunner:
 
     def save(self, path, infos=None):
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        torch.save({"model_state_dict": self.alg.actor_critic.state_dict(),
-                    "optimizer_state_dict": self.alg.optimizer.state_dict(),
-                    "iter": self.current_learning_iteration, "infos": infos}, path)
+        saved = {"model_state_dict": self.alg.actor_critic.state_dict(),
+                 "optimizer_state_dict": self.alg.optimizer.state_dict(),
+                 "iter": self.current_learning_iteration, "infos": infos}
+        if getattr(self.alg, "rnd", None) is not None:  # rsl_rl 2.x's key names
+            saved["rnd_state_dict"] = self.alg.rnd.state_dict()
+            saved["rnd_optimizer_state_dict"] = self.alg.rnd_optimizer.state_dict()
+        torch.save(saved, path)
 
     def load(self, path, load_optimizer=True):
         loaded = torch.load(path, map_location=self.device, weights_only=True)
@@ -447,6 +461,17 @@ class OnPolicyRunner:
             if getattr(self.alg, "_graph", None) is not None:
                 self.alg._graph = None
         self.current_learning_iteration = loaded["iter"]
+        if getattr(self.alg, "rnd", None) is not None:
+            if "rnd_state_dict" in loaded:
+                self.alg.rnd.load_state_dict(loaded["rnd_state_dict"])
+                if load_optimizer and "rnd_optimizer_state_dict" in loaded:
+                    self.alg.rnd_optimizer.load_state_dict(loaded["rnd_optimizer_state_dict"])
+                self.alg.rnd_loaded()
+            else:
+                warnings.warn("OnPolicyRunner.load: the checkpoint holds no rnd_state_dict; the policy is loaded "
+                              "and the RND nets stay freshly initialised")
+            # the weight schedule counts env steps from the loaded iteration
+            self.alg.rnd_iteration = self.current_learning_iteration
         return loaded["infos"]
 
     def get_inference_policy(self, device=None):
