@@ -105,6 +105,27 @@ PMLP_API int pmlp_gemm(int32_t epi, int32_t njobs, const pmlp_gemm_job* jobs, in
  * those of the two launches. */
 PMLP_API int pmlp_gemm_pair(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
                             const pmlp_gemm_job* jobs_x, void* stream);
+/* pmlp_gemm_pair for the layer above the first, with the first layer's weight gradient: jobs_w0[i]
+ * (PARTIAL_TN, ksplit0 rows per slab) is the weight gradient whose A is the input gradient
+ * jobs_x[i] produces (A and lda are ignored; M = jobs_x[i].N, K = jobs_x[i].M), and gives B (the
+ * first layer's bf16 input rows), cf (the slab base), ldcf and sum_col.
+ * Folded (*folded = 1): the input-gradient tiles form those slabs from their bf16 result while it
+ * is in LDS, so that gradient need not be stored (jobs_x' cb and ct may both be NULL) and no
+ * second launch reads it back.  A workgroup runs the 128-row tiles of one slab in ascending order:
+ * the slabs and the sum_col column are bitwise those of pmlp_gemm(PARTIAL_TN) on the stored cb.
+ * It folds when allow_fold != 0, the 128 x 128 LDS-DMA tile fits the input gradient (N a multiple
+ * of 128, K of 64, LDS-DMA staging on; it is taken whatever the grid's size), every jobs_x job has
+ * the same M, N, K, ldcf <= 64, ksplit0 is a multiple of 128 and M a multiple of ksplit0; jobs_w
+ * run beside it where they take the 128 x 128 LDS-DMA tile too, else as their own launch first.
+ * Otherwise (*folded = 0) it runs pmlp_gemm_pair, then pmlp_gemm(PARTIAL_TN, jobs_w0) with
+ * A = jobs_x[i].cb, which must then be given.  folded may be NULL. */
+PMLP_API int pmlp_gemm_pair_dw0(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
+                                const pmlp_gemm_job* jobs_x, int32_t njobs_w0, const pmlp_gemm_job* jobs_w0,
+                                int32_t ksplit0, int32_t allow_fold, int32_t* folded, void* stream);
+/* whether that call (with allow_fold != 0) would fold: 1 / 0, or a negative status; launches nothing */
+PMLP_API int pmlp_gemm_pair_dw0_plan(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
+                                     const pmlp_gemm_job* jobs_x, int32_t njobs_w0, const pmlp_gemm_job* jobs_w0,
+                                     int32_t ksplit0);
 /* operand staging of pmlp_gemm's k-loop: 1 (the default; no environment variable is read) = LDS-DMA
  * into two LDS buffers, one barrier per k-tile, wherever the shapes allow (whole 64-deep k-tiles);
  * 0 = register staging; 2 = LDS-DMA only for PARTIAL_TN, as a ring of four buffers; 3 = that ring

@@ -94,6 +94,20 @@ struct GemmBatch {
     int slabs;  // PARTIAL: slabs per job (grid.z = njobs * slabs)
 };
 
+// The first layer's weight gradient folded into the layer-1 input gradient (gemm_tile's FOLD):
+// job i's first-layer input xb [rows][N] (the PARTIAL_TN B operand), its slabs cf
+// [slab][Mw][ldcf] and the slab column of the bias gradient (0 = none); `tiles` 128-row tiles
+// make one slab.
+struct FoldArgs {
+    const bf16* xb;
+    float* cf;
+    int ldxb, ldcf, N, sumc, Mw;
+};
+struct FoldBatch {
+    FoldArgs j[PMLP_MAX_GEMM_JOBS];
+    int tiles;
+};
+
 // ds_read_b64_tr_b16 (guide T10): per 16-lane group, lane 4q+p addresses row q,
 // columns 4p..4p+3 of a 4 x 16 block; lane i receives column i, rows 0..3
 __device__ __forceinline__ shortx4 lds_read_tr(const bf16* p) {
@@ -138,7 +152,7 @@ __device__ __forceinline__ int gl_swz(int r) { return R == 128 ? (r & 3) : ((r >
 // operand, R a multiple of the tile (rows-form tiles past M / N read a clamped row instead;
 // those outputs are never stored).  Same MFMA order as GL = 0: bitwise the same results.
 // LDS elements (bf16) of one k_gemm_nt tile: the staging buffers, or the epilogue tiles
-template <int BM, int BN, int WM, int WN, int EPI, int NKS, int MODE, int GL>
+template <int BM, int BN, int WM, int WN, int EPI, int NKS, int MODE, int GL, bool FOLD = false>
 __host__ __device__ constexpr int gemm_smem() {
     constexpr bool TNL = EPI == PMLP_EPI_PARTIAL_TN, PART = EPI == PMLP_EPI_PARTIAL || TNL;
     constexpr bool BKN = TNL || (MODE & 2) != 0;
@@ -147,35 +161,26 @@ __host__ __device__ constexpr int gemm_smem() {
     constexpr int ATILE = TNL ? BK * SA : BM * LS, BTILE = BKN ? BK * SB : BN * LS;
     constexpr int GSTAGE = (BM + BN) * BK, GNS = GL == 2 ? 4 : 2;
     constexpr int STAGE = GL ? GNS * GSTAGE : (ATILE + BTILE) * PMLP_NBUF, CTILE = BM * (BN + 8), TTILE = BN * (BM + 8);
-    return PART ? STAGE : (STAGE > CTILE ? (STAGE > TTILE ? STAGE : TTILE) : (CTILE > TTILE ? CTILE : TTILE));
+    constexpr int BASE = PART ? STAGE : (STAGE > CTILE ? (STAGE > TTILE ? STAGE : TTILE) : (CTILE > TTILE ? CTILE : TTILE));
+    constexpr int FTILE = (CTILE > TTILE ? CTILE : TTILE) + BM * (64 + 32);  // FOLD: + the k-major xb image
+    return FOLD && FTILE > BASE ? FTILE : BASE;
 }
 
-// One output tile of the batched GEMM: block b of a gx x gy x gz grid (b linear), smem the
-// gemm_smem<...>() bf16 elements of LDS.  k_gemm_nt runs it as a kernel of its own;
-// k_gemm_pair runs two of them (a weight gradient beside an input gradient) in one grid.
-template <int BM, int BN, int WM, int WN, int EPI, int NKS = 4, int MODE = 0, int GL = 0>
-__device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b, int gx, int gy, int gz) {
-    // XCD-aware tile order: blocks are dealt round-robin over the 8 XCDs (b % 8), each
-    // with its own L2; give every XCD a contiguous range of logical tiles, ordered so that
-    // the tiles sharing an operand panel are neighbours -- the n-tiles of one row block
-    // (forward / input gradient: they share the A rows), the tiles of one split-K slab
-    // (weight gradient: they share its rows of both operands) -- and read it from one L2.
-    // (In a paired grid b is the block's index within its half: the halves' XCDs are
-    // rotated by the offset, each XCD still owns one contiguous range.)
-    int bx, by, bz;
-    {
-        const int nwg = gx * gy * gz;
-        const int xcd = b % 8, q = nwg / 8, r = nwg % 8;
-        const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-        if (EPI == PMLP_EPI_PARTIAL || EPI == PMLP_EPI_PARTIAL_TN) {
-            bx = L % gx; by = (L / gx) % gy;
-        } else {
-            by = L % gy; bx = (L / gy) % gx;
-        }
-        bz = L / (gx * gy);
-    }
-    const int job = bz / gb.slabs, slice = bz % gb.slabs;
-    const GemmArgs& g = gb.j[job];
+// One output tile of the batched GEMM: tile (bx, by) of job g (split-K slab `slice`), smem
+// the gemm_smem<...>() bf16 elements of LDS.  gemm_tile (below) maps a block to its tile:
+// k_gemm_nt runs it as a kernel of its own; k_gemm_pair runs two of them (a weight gradient
+// beside an input gradient) in one grid.
+//
+// FOLD (BWD_DX on 128 x 128 tiles of 8 waves): the tile's bf16 result, staged [BM][CS] in LDS
+// for cb, is the k-major A operand of the NEXT layer's weight gradient (PARTIAL_TN: k = the
+// row), so that product is formed here from the tile while it is on chip -- `fa` its B rows
+// and slabs, `facc` the wave's 32 x 32 block of the [BN][64] slab piece, accumulated over the
+// row tiles the caller runs in ascending order.  The bias gradient is the slab column sumc of
+// the same MFMAs: the xb image carries ones there, so that column is the ones product of
+// PARTIAL_TN's sum_col.  cb and ct become optional.
+template <int BM, int BN, int WM, int WN, int EPI, int NKS = 4, int MODE = 0, int GL = 0, bool FOLD = false>
+__device__ __forceinline__ void gemm_tile_at(const GemmArgs& g, bf16* smem, int slice, int bx, int by,
+                                             const FoldArgs* fa = nullptr, floatx16* facc = nullptr) {
     if (bx * BM >= g.M || by * BN >= g.N) return;  // grid covers the largest job
     // PARTIAL_TN: A[K,M] and B[K,N] (m / n contiguous: the row-major activations and
     // gradients), staged k-major in LDS and fed to the MFMAs by transposed reads
@@ -212,10 +217,20 @@ __device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b
     constexpr int SMEM = PART ? STAGE
                               : (STAGE > CTILE ? (STAGE > TTILE ? STAGE : TTILE) : (CTILE > TTILE ? CTILE : TTILE));
     static_assert(SMEM == gemm_smem<BM, BN, WM, WN, EPI, NKS, MODE, GL>(), "gemm_smem out of step");
+    // FOLD: the xb rows of this tile, k-major [BM][XS] behind the epilogue tiles (the stride
+    // of PARTIAL_TN's B image at BN = 64)
+    constexpr int XS = 64 + 32, XOFF = CTILE > TTILE ? CTILE : TTILE;
+    static_assert(!FOLD || (EPI == PMLP_EPI_BWD_DX && BM == 128 && BN == 128 && WM * WN == 8 && (CS * 2) % 8 == 0),
+                  "FOLD: the 128 x 128 BWD_DX tile of 8 waves");
+    static_assert(!FOLD || XOFF + BM * XS <= gemm_smem<BM, BN, WM, WN, EPI, NKS, MODE, GL, FOLD>(), "FOLD image past the LDS");
     bf16* As = smem;
     bf16* Bs = smem + ATILE;
 
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int tid_ = threadIdx.x;
+    // FOLD runs this body once per row tile: the lane's addresses are derived again in each
+    // (opaque here), not kept in registers across the tiles beside the fold's accumulators
+    if constexpr (FOLD) asm volatile("" : "+v"(tid_));
+    const int tid = tid_, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
     const int m0 = bx * BM, n0 = by * BN;
     int kb = 0, ke = g.K;
@@ -625,6 +640,18 @@ __device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b
                     }
             }
         } else {  // BWD_DX: ELU' from the staged y tile, 4 columns per LDS read
+            // FOLD: this tile's xb rows (16-byte chunks of 8 columns, zero past N as PARTIAL_TN
+            // stages them), in flight while ELU' is applied
+            constexpr int XL = FOLD ? BM * 8 / NT : 1;
+            uint4 xr[XL];
+            if constexpr (FOLD) {
+#pragma unroll
+                for (int u = 0; u < XL; ++u) {
+                    const int c = tid + u * NT, r = c >> 3, cc = (c & 7) * 8;
+                    xr[u] = cc < fa->N ? *(const uint4*)(fa->xb + (size_t)(m0 + r) * fa->ldxb + cc)
+                                       : make_uint4(0, 0, 0, 0);
+                }
+            }
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -640,7 +667,7 @@ __device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b
                         }
                     }
             __syncthreads();  // y tile consumed before the LDS is rewritten
-            if (g.cb) {
+            if (FOLD || g.cb) {
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -653,8 +680,33 @@ __device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b
                             for (int u = 0; u < 4; ++u) o[u] = (bf16)acc[i][j][4 * q + u];
                             *(bf16x4*)(smem + lr * CS + lc) = o;
                         }
+                if constexpr (FOLD) {
+#pragma unroll
+                    for (int u = 0; u < XL; ++u) {
+                        const int c = tid + u * NT, r = c >> 3, cc = (c & 7) * 8;
+                        bf16* dst = smem + XOFF + r * XS;
+                        *(uint4*)(dst + cc) = xr[u];
+                        // (after this thread's own chunk: LDS writes of one wave land in order)
+                        if (fa->sumc > 0 && (fa->sumc >> 3) == (c & 7)) dst[fa->sumc] = (bf16)1.f;
+                    }
+                }
                 __syncthreads();
-                cb_out();
+                if (!FOLD || g.cb) cb_out();
+                if constexpr (FOLD) {
+                    // the tile as PARTIAL_TN's A image (k = its rows, stride CS), the xb image
+                    // as its B: wave (fm, fn) owns features 32 fm.., slab columns 32 fn..
+                    const int fm = wid >> 1, fn = wid & 1;
+#pragma unroll
+                    for (int s = 0; s < BM / 16; ++s) {
+                        const bf16* pa = smem + (s * 16 + tr_off) * CS + fm * 32 + tr_col;
+                        const bf16* pb = smem + XOFF + (s * 16 + tr_off) * XS + fn * 32 + tr_col;
+                        const shortx4 alo = lds_read_tr(pa), ahi = lds_read_tr(pa + 4 * CS);
+                        const shortx4 blo = lds_read_tr(pb), bhi = lds_read_tr(pb + 4 * XS);
+                        const bf16x8 fa8 = __builtin_bit_cast(bf16x8, __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7));
+                        const bf16x8 fb8 = __builtin_bit_cast(bf16x8, __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7));
+                        *facc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb8, fa8, *facc, 0, 0, 0);
+                    }
+                }
                 if (g.ct) __syncthreads();
             }
             if (g.ct) {
@@ -738,6 +790,76 @@ __device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b
     }
 }
 
+// Block b of a gx x gy x gz grid (b linear) -> its tile (bx, by) of job / slab bz.
+// XCD-aware tile order: blocks are dealt round-robin over the 8 XCDs (b % 8), each
+// with its own L2; give every XCD a contiguous range of logical tiles, ordered so that
+// the tiles sharing an operand panel are neighbours -- the n-tiles of one row block
+// (forward / input gradient: they share the A rows), the tiles of one split-K slab
+// (weight gradient: they share its rows of both operands) -- and read it from one L2.
+// (In a paired grid b is the block's index within its half: the halves' XCDs are
+// rotated by the offset, each XCD still owns one contiguous range.)
+template <int EPI>
+__device__ __forceinline__ void gemm_tile_of(int b, int gx, int gy, int gz, int& bx, int& by, int& bz) {
+    const int nwg = gx * gy * gz;
+    const int xcd = b % 8, q = nwg / 8, r = nwg % 8;
+    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+    if (EPI == PMLP_EPI_PARTIAL || EPI == PMLP_EPI_PARTIAL_TN) {
+        bx = L % gx; by = (L / gx) % gy;
+    } else {
+        by = L % gy; bx = (L / gy) % gx;
+    }
+    bz = L / (gx * gy);
+}
+
+template <int BM, int BN, int WM, int WN, int EPI, int NKS = 4, int MODE = 0, int GL = 0>
+__device__ __forceinline__ void gemm_tile(const GemmBatch& gb, bf16* smem, int b, int gx, int gy, int gz) {
+    int bx, by, bz;
+    gemm_tile_of<EPI>(b, gx, gy, gz, bx, by, bz);
+    gemm_tile_at<BM, BN, WM, WN, EPI, NKS, MODE, GL>(gb.j[bz / gb.slabs], smem, bz % gb.slabs, bx, by);
+}
+
+// The FOLD form of a BWD_DX batch: block (bx, by) of job bz owns column tile by and the next
+// layer's split-K slab bx, runs that slab's fb.tiles row tiles in ascending order (the k order
+// of the PARTIAL_TN launch it replaces) and stores its [BN][ldcf] piece of the slab: no
+// atomics, no hand-off between workgroups.  Every job has the same M (a multiple of the slab).
+template <int BM, int BN, int WM, int WN, int EPI, int NKS, int MODE, int GL>
+__device__ __forceinline__ void gemm_tile_fold(const GemmBatch& gb, const FoldBatch& fb, bf16* smem, int b, int gx,
+                                               int gy, int gz) {
+    int bx, by, bz;
+    gemm_tile_of<EPI>(b, gx, gy, gz, bx, by, bz);
+    const GemmArgs& g = gb.j[bz];
+    const FoldArgs& fa = fb.j[bz];
+    if (by * BN >= g.N) return;
+    floatx16 facc;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) facc[t] = 0.f;
+    for (int rt = 0; rt < fb.tiles; ++rt) {
+        gemm_tile_at<BM, BN, WM, WN, EPI, NKS, MODE, GL, true>(g, smem, 0, bx * fb.tiles + rt, by, &fa, &facc);
+        __syncthreads();  // the tile's LDS is read before the next tile's k-loop refills it
+    }
+    // C^T accumulators (as PARTIAL_TN's): lane -> feature row, 4 consecutive slab columns per quad
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int row = by * BN + (wid >> 1) * 32 + (lane & 31), c0 = (wid & 1) * 32 + 4 * (lane >> 5);
+    float* dst = fa.cf + ((size_t)bx * fa.Mw + row) * fa.ldcf;
+    const bool vec = (fa.ldcf & 3) == 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int col = c0 + 8 * q;
+        const float a[4] = {facc[4 * q], facc[4 * q + 1], facc[4 * q + 2], facc[4 * q + 3]};
+        if (!PMLP_STORE_OK) continue;
+        if (vec && col + 4 <= fa.N) {
+            *(float4*)(dst + col) = make_float4(a[0], a[1], a[2], a[3]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (col + u < fa.N) dst[col + u] = a[u];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (fa.sumc > 0 && col + u == fa.sumc) dst[col + u] = a[u];
+    }
+}
+
 template <int BM, int BN, int WM, int WN, int EPI, int NKS = 4, int MODE = 0, int GL = 0>
 __global__ __launch_bounds__(64 * WM* WN) void k_gemm_nt(GemmBatch gb) {
     __shared__ __attribute__((aligned(16))) bf16 smem[gemm_smem<BM, BN, WM, WN, EPI, NKS, MODE, GL>()];
@@ -768,6 +890,27 @@ __global__ __launch_bounds__(CA::NT) void k_gemm_pair(GemmBatch ga, GemmBatch gb
     const int b = blockIdx.x;
     if (b < nA) CA::run(ga, smem, b, dA.x, dA.y, dA.z);
     else CB::run(gbb, smem, b - nA, dB.x, dB.y, dB.z);
+}
+
+// k_gemm_pair whose input-gradient half also forms the next (first) layer's weight-gradient
+// slabs (gemm_tile_fold): dB = (slabs, column tiles, jobs)
+// (4 waves per SIMD: two workgroups per CU as k_gemm_pair has, VGPRs <= 128)
+template <class CA, int BM, int BN, int WM, int WN, int EPI, int NKS, int MODE, int GL>
+__global__ __launch_bounds__(CA::NT, 4) void k_gemm_pair_fold(GemmBatch ga, GemmBatch gbb, FoldBatch fb, int nA, int3 dA,
+                                                           int3 dB) {
+    static_assert(CA::NT == 64 * WM * WN, "paired halves need one block size");
+    constexpr int SB = gemm_smem<BM, BN, WM, WN, EPI, NKS, MODE, GL, true>();
+    __shared__ __attribute__((aligned(16))) bf16 smem[CA::SMEM > SB ? CA::SMEM : SB];
+    const int b = blockIdx.x;
+    if (b < nA) CA::run(ga, smem, b, dA.x, dA.y, dA.z);
+    else gemm_tile_fold<BM, BN, WM, WN, EPI, NKS, MODE, GL>(gbb, fb, smem, b - nA, dB.x, dB.y, dB.z);
+}
+
+// That half as a kernel of its own (a weight gradient whose tiles do not pair runs in its own launch)
+template <int BM, int BN, int WM, int WN, int EPI, int NKS, int MODE, int GL>
+__global__ __launch_bounds__(64 * WM* WN, 4) void k_gemm_nt_fold(GemmBatch gb, FoldBatch fb, int3 d) {
+    __shared__ __attribute__((aligned(16))) bf16 smem[gemm_smem<BM, BN, WM, WN, EPI, NKS, MODE, GL, true>()];
+    gemm_tile_fold<BM, BN, WM, WN, EPI, NKS, MODE, GL>(gb, fb, smem, blockIdx.x, d.x, d.y, d.z);
 }
 
 // Batched fp32 -> bf16 conversion, 64x64 tiles through LDS (blockIdx.z = job):
@@ -1921,8 +2064,9 @@ PMLP_API int pmlp_convert(int32_t njobs, const pmlp_convert_job* jobs, void* str
 }  // extern "C"
 
 // pmlp_gemm's argument checks and packing: one batch of jobs -> GemmBatch (+ its extents)
+// (out_optional: a BWD_DX batch may come without cb and ct -- pmlp_gemm_pair_dw0's folded path)
 static int gemm_pack(int32_t epi, int32_t njobs, const pmlp_gemm_job* jobs, int32_t ksplit, GemmBatch& gb, int& maxm,
-                     int& maxn, int& maxk, int& mode) {
+                     int& maxn, int& maxk, int& mode, bool out_optional = false) {
     if (epi < 0 || epi > 4) return fail(-1, "pmlp_gemm: unknown epilogue");
     const bool part = epi == PMLP_EPI_PARTIAL || epi == PMLP_EPI_PARTIAL_TN;
     if (njobs <= 0 || njobs > PMLP_MAX_GEMM_JOBS || !jobs) return fail(-1, "pmlp_gemm: 1..PMLP_MAX_GEMM_JOBS jobs");
@@ -1960,7 +2104,7 @@ static int gemm_pack(int32_t epi, int32_t njobs, const pmlp_gemm_job* jobs, int3
         if ((epi == PMLP_EPI_FWD_OUT || part) && (!J.cf || J.ldcf < J.N))
             return fail(-1, w + "fp32 output missing or ldcf < N");
         if ((epi == PMLP_EPI_FWD_HIDDEN || epi == PMLP_EPI_BWD_DX) &&
-            ((!J.cb && !J.ct) || (J.cb && J.ldcb < J.N) || (J.ct && (J.ldct < J.M || J.ldct % 4))))
+            ((!J.cb && !J.ct && !out_optional) || (J.cb && J.ldcb < J.N) || (J.ct && (J.ldct < J.M || J.ldct % 4))))
             return fail(-1, w + "bf16 output missing or bad leading dimension");
         if (epi == PMLP_EPI_BWD_DX && (!J.yprev || J.ldyp < J.N)) return fail(-1, w + "BWD_DX needs yprev");
         GemmArgs& g = gb.j[i];
@@ -2063,6 +2207,86 @@ PMLP_API int pmlp_gemm_pair(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_
     }
     PMLP_CHECK_LAUNCH("pmlp_gemm_pair");
     return 0;
+}
+
+}  // extern "C"
+
+// pmlp_gemm_pair_dw0 and its plan: 1 = folded (launched unless `dry`), 0 = the two launches
+static int gemm_pair_dw0(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
+                         const pmlp_gemm_job* jobs_x, int32_t njobs_w0, const pmlp_gemm_job* jobs_w0, int32_t ksplit0,
+                         int32_t allow_fold, bool dry, void* stream) {
+    GemmBatch gw, gx;
+    int mmw, mnw, mkw, modew, mmx, mnx, mkx, modex;
+    if (const int rc = gemm_pack(PMLP_EPI_PARTIAL_TN, njobs_w, jobs_w, ksplit, gw, mmw, mnw, mkw, modew)) return rc;
+    if (const int rc = gemm_pack(PMLP_EPI_BWD_DX, njobs_x, jobs_x, 0, gx, mmx, mnx, mkx, modex, true)) return rc;
+    if (njobs_w0 != njobs_x || !jobs_w0) return fail(-1, "pmlp_gemm_pair_dw0: one first-layer job per input-gradient job");
+    FoldBatch fb{};
+    // the input gradient on plan 4's tile (128 x 128, LDS-DMA), whatever the grid's size: a
+    // folded workgroup runs a whole slab's row tiles
+    bool fold = allow_fold != 0 && modex == 2 && gl_fits<128, 128>(PMLP_EPI_BWD_DX, modex, gx, njobs_x) && ksplit0 > 0 &&
+                ksplit0 % 128 == 0;
+    for (int i = 0; i < njobs_x; ++i) {
+        const pmlp_gemm_job &X = jobs_x[i], &J = jobs_w0[i];
+        const std::string w = "pmlp_gemm_pair_dw0 first-layer job " + std::to_string(i) + ": ";
+        // its A is the input gradient itself: dz[K = X.M rows][M = X.N features]
+        if (J.af || J.b_kn || !J.B || !J.cf || J.N <= 0 || J.M != X.N || J.K != X.M || J.ldcf < J.N || J.ldb % 8 ||
+            J.ldb < (J.N + 7) / 8 * 8 || !al16(J.B))
+            return fail(-1, w + "B [K,N] (ldb >= ceil8(N), a multiple of 8, 16-byte aligned) and cf, with M, K the "
+                                "input gradient's N, M");
+        if (J.sum_col && (J.sum_col < J.N || J.sum_col >= J.ldcf)) return fail(-1, w + "sum_col: N <= sum_col < ldcf");
+        fold = fold && X.M == jobs_x[0].M && X.N == jobs_x[0].N && X.K == jobs_x[0].K && X.M % ksplit0 == 0 &&
+               J.ldcf <= 64;
+        fb.j[i] = FoldArgs{(const bf16*)J.B, J.cf, J.ldb, J.ldcf, J.N, J.sum_col, J.M};
+    }
+    if (dry) return fold ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (fold) {
+        using CA = GemmCfg<128, 128, 2, 4, PMLP_EPI_PARTIAL_TN, 4, 0, 1>;
+        fb.tiles = ksplit0 / 128;
+        const dim3 db(mmx / ksplit0, mnx / 128, njobs_x);
+        const int nb = (int)(db.x * db.y * db.z);
+        const int3 d3 = make_int3((int)db.x, (int)db.y, (int)db.z);
+        if (gemm_plan(PMLP_EPI_PARTIAL_TN, modew, gw, njobs_w, mmw, mnw, mkw) == 3) {  // beside plan 4, as pmlp_gemm_pair
+            const dim3 da = gemm_grid(CA::BM, CA::BN, gw, njobs_w, mmw, mnw);
+            const int na = (int)(da.x * da.y * da.z);
+            hipLaunchKernelGGL((k_gemm_pair_fold<CA, 128, 128, 2, 4, PMLP_EPI_BWD_DX, 4, 2, 1>), dim3(na + nb), dim3(CA::NT),
+                               0, st, gw, gx, fb, na, make_int3((int)da.x, (int)da.y, (int)da.z), d3);
+        } else {
+            if (const int rc = pmlp_gemm(PMLP_EPI_PARTIAL_TN, njobs_w, jobs_w, ksplit, stream)) return rc;
+            hipLaunchKernelGGL((k_gemm_nt_fold<128, 128, 2, 4, PMLP_EPI_BWD_DX, 4, 2, 1>), dim3(nb), dim3(512), 0, st, gx, fb,
+                               d3);
+        }
+        PMLP_CHECK_LAUNCH("pmlp_gemm_pair_dw0");
+        return 1;
+    }
+    pmlp_gemm_job w0[PMLP_MAX_GEMM_JOBS];
+    for (int i = 0; i < njobs_x; ++i) {
+        if (!jobs_x[i].cb) return fail(-1, "pmlp_gemm_pair_dw0: the two launches need the input gradient's cb");
+        w0[i] = jobs_w0[i];
+        w0[i].A = jobs_x[i].cb;
+        w0[i].lda = jobs_x[i].ldcb;
+    }
+    if (const int rc = pmlp_gemm_pair(njobs_w, jobs_w, ksplit, njobs_x, jobs_x, stream)) return rc;
+    if (const int rc = pmlp_gemm(PMLP_EPI_PARTIAL_TN, njobs_x, w0, ksplit0, stream)) return rc;
+    return 0;
+}
+
+extern "C" {
+
+PMLP_API int pmlp_gemm_pair_dw0(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
+                                const pmlp_gemm_job* jobs_x, int32_t njobs_w0, const pmlp_gemm_job* jobs_w0,
+                                int32_t ksplit0, int32_t allow_fold, int32_t* folded, void* stream) {
+    const int rc = gemm_pair_dw0(njobs_w, jobs_w, ksplit, njobs_x, jobs_x, njobs_w0, jobs_w0, ksplit0, allow_fold, false,
+                                 stream);
+    if (rc < 0) return rc;
+    if (folded) *folded = rc;
+    return 0;
+}
+
+PMLP_API int pmlp_gemm_pair_dw0_plan(int32_t njobs_w, const pmlp_gemm_job* jobs_w, int32_t ksplit, int32_t njobs_x,
+                                     const pmlp_gemm_job* jobs_x, int32_t njobs_w0, const pmlp_gemm_job* jobs_w0,
+                                     int32_t ksplit0) {
+    return gemm_pair_dw0(njobs_w, jobs_w, ksplit, njobs_x, jobs_x, njobs_w0, jobs_w0, ksplit0, 1, true, nullptr);
 }
 
 static int reduce_pack(int32_t njobs, const pmlp_reduce_job* jobs, RedJobs& rj, int64_t& nb) {

@@ -12,7 +12,11 @@ What runs here (csrc/ppo_mlp.hip through include/ppo_mlp.h):
     2 + 2       loss forward (+ final) / backward (+ std gradient); the loss
                 reads actions, old log-probs, advantages, ... through the index
     1 convert   output gradients to bf16
-    2L-1 GEMMs  weight-gradient slabs and input gradients
+    2L-1 GEMMs  weight-gradient slabs and input gradients (L launches where a layer's
+                two share one, pmlp_gemm_pair; L-1 where the first layer's weight
+                gradient is formed inside layer 1's input-gradient tiles,
+                pmlp_gemm_pair_dw0: the gradient at the first hidden layer's output
+                is then never written to memory)
     2           slab combine + bias sums, written into the flat gradient
     2           grad-norm partials (+ step/LR/loss bookkeeping) and Adam
 
@@ -153,7 +157,9 @@ class FusedPPOStep:
         self.loss_partial = torch.empty(mm.load().pmlp_ppo_loss_step_parts(M, A), device=dev)
         # output gradients (bf16) and the hidden-layer input gradients
         self.dz_out = [torch.empty(M, _ceil8(ls[-1].out_features), dtype=bf, device=dev) for ls in self.lins]
-        self.dz = [[torch.empty(M, lin.in_features, dtype=bf, device=dev) if l > 0 else None
+        # (dz[n][1], the gradient at the first hidden layer's output, only where the first layer's
+        # weight gradient is not folded into the launch that forms it: below)
+        self.dz = [[torch.empty(M, lin.in_features, dtype=bf, device=dev) if l > 1 else None
                     for l, lin in enumerate(ls)] for ls in self.lins]
         # split-K weight-gradient slabs; layers whose padded width differs from the
         # parameter's get a staging buffer (copied into the flat gradient)
@@ -163,6 +169,8 @@ class FusedPPOStep:
             # (the bias column is the TN kernel's ones product, not an extra column tile)
             ks = mm._ksplit(M, max(mm._tiles(self.lins[n][l].out_features, kps[n]) for n in range(2)),
                             slab_bytes=max(4 * self.lins[n][l].out_features * (kps[n] + 8) for n in range(2)))
+            if l == 0 and os.environ.get("PMLP_KS0"):  # (A/B runs: rows per first-layer slab)
+                ks = int(os.environ["PMLP_KS0"])
             nsl = (M + ks - 1) // ks
             self.ks.append(ks)
             self.slab.append([torch.empty(nsl, self.lins[n][l].out_features, kps[n] + 8, device=dev)
@@ -210,6 +218,36 @@ class FusedPPOStep:
         self.loss_nb = (fl_parts if self.fused_loss else self.loss_partial.numel()) // (3 + A)
         # a layer's weight and input gradients in one launch (PMLP_GEMM_PAIR=0: two launches)
         self.pair_backward = os.environ.get("PMLP_GEMM_PAIR", "1") != "0"
+        # the first layer's weight gradient inside layer 1's input-gradient tiles
+        # (pmlp_gemm_pair_dw0; PMLP_DW0_FOLD=0: its own launch, reading dz[n][1] back): dz[n][1]
+        # is then never stored.  A first layer wider than 56 inputs keeps the two launches.
+        self.dw0_fold = False
+        if L >= 2 and self.pair_backward and os.environ.get("PMLP_DW0_FOLD", "1") != "0":
+            dz2 = self.dz_out if L == 2 else [self.dz[n][2] for n in range(2)]
+            self.dw0_fold = mm._gemm_pair_dw0(self._dw_jobs(1, dz2, self.xb), self.ks[1], self._dx_jobs(1, dz2),
+                                              self._dw_jobs(0, None, self.xb), self.ks[0], plan=True)
+        if L >= 2 and not self.dw0_fold:
+            for n in range(2):
+                self.dz[n][1] = torch.empty(M, self.lins[n][1].in_features, dtype=bf, device=dev)
+
+    def _dw_jobs(self, l, dz, xb):
+        """Layer l's weight-gradient jobs (PARTIAL_TN): A = dz [M, out] (None: implied, the folded
+        first layer), B = the layer's input [M, kp], both row-major; the slab's column kp
+        receives the bias gradient."""
+        gj = []
+        for n in range(2):
+            lin = self.lins[n][l]
+            kp = self.k0p[n] if l == 0 else lin.in_features
+            a = {} if dz is None else dict(A=dz[n])
+            gj.append(dict(B=xb[n] if l == 0 else self.y[n][l - 1], M=lin.out_features, N=kp, K=self.M,
+                           cf=self.slab[l][n], sum_col=kp, **a))
+        return gj
+
+    def _dx_jobs(self, l, dz):
+        """Layer l's input-gradient jobs (BWD_DX on W[out, in] itself); cb = dz[n][l], or none
+        where the folded first-layer weight gradient is its only reader."""
+        return [dict(A=dz[n], B=self.wb[n][l], b_kn=1, M=self.M, N=self.lins[n][l].in_features, K=dz[n].shape[1],
+                     yprev=self.y[n][l - 1], cb=self.dz[n][l]) for n in range(2)]
 
     # -------------------------------------------------------- optimizer state --
     def sync_optimizer_state(self, opt):
@@ -313,23 +351,19 @@ class FusedPPOStep:
         dz = list(self.dz_out)
         red, copies = self.red, self.copies
         for l in range(L - 1, -1, -1):
-            gj = []
-            for n in range(2):
-                lin = self.lins[n][l]
-                kp = self.k0p[n] if l == 0 else lin.in_features
-                # A = dz [M, out], B = activations [M, kp] (row-major)
-                B = xb[n] if l == 0 else self.y[n][l - 1]
-                gj.append(dict(A=dz[n], B=B, M=lin.out_features, N=kp, K=M, cf=self.slab[l][n], sum_col=kp))
+            if l == 0 and self.dw0_fold:
+                break  # (formed in layer 1's launch)
+            gj = self._dw_jobs(l, dz, xb)
             if l == 0:
                 mm._gemm(mm.EPI_PARTIAL_TN, gj, ksplit=self.ks[l])
             else:
-                gx = []
-                for n in range(2):
-                    lin = self.lins[n][l]
-                    # the input layer's gradient is only consumed transposed (its weight gradient)
-                    gx.append(dict(A=dz[n], B=self.wb[n][l], b_kn=1, M=M, N=lin.in_features, K=dz[n].shape[1],
-                                   yprev=self.y[n][l - 1], cb=self.dz[n][l]))
-                if self.pair_backward:
+                gx = self._dx_jobs(l, dz)
+                if l == 1 and self.dw0_fold:
+                    # the first layer's weight gradient is the only reader of this input gradient:
+                    # formed from its tiles on chip, which are not stored (no cb)
+                    if not mm._gemm_pair_dw0(gj, self.ks[1], gx, self._dw_jobs(0, None, xb), self.ks[0]):
+                        raise RuntimeError("fused PPO step: the planned first-layer fold did not apply")
+                elif self.pair_backward:
                     mm._gemm_pair(gj, self.ks[l], gx)
                 else:
                     mm._gemm(mm.EPI_PARTIAL_TN, gj, ksplit=self.ks[l])

@@ -140,6 +140,10 @@ def load():
         L.pmlp_convert.argtypes = [i32, C.POINTER(ConvertJob), vp]
         L.pmlp_gemm.argtypes = [i32, i32, C.POINTER(GemmJob), i32, vp]
         L.pmlp_gemm_pair.argtypes = [i32, C.POINTER(GemmJob), i32, i32, C.POINTER(GemmJob), vp]
+        L.pmlp_gemm_pair_dw0.argtypes = [i32, C.POINTER(GemmJob), i32, i32, C.POINTER(GemmJob), i32, C.POINTER(GemmJob),
+                                         i32, i32, C.POINTER(i32), vp]
+        L.pmlp_gemm_pair_dw0_plan.argtypes = [i32, C.POINTER(GemmJob), i32, i32, C.POINTER(GemmJob), i32,
+                                              C.POINTER(GemmJob), i32]
         L.pmlp_reduce_slabs.argtypes = [i32, C.POINTER(ReduceJob), vp]
         L.pmlp_reduce_slabs_step.argtypes = [i32, C.POINTER(ReduceJob), C.POINTER(ReduceStep), vp]
         L.pmlp_reduce_slabs_parts.argtypes = [i32, C.POINTER(ReduceJob)]
@@ -337,6 +341,26 @@ def _gemm_pair(jobs_w, ksplit, jobs_x):
     aw = (GemmJob * len(jobs_w))(*[_gemm_job(j) for j in jobs_w])
     ax = (GemmJob * len(jobs_x))(*[_gemm_job(j) for j in jobs_x])
     _ok(load().pmlp_gemm_pair(len(jobs_w), aw, ksplit, len(jobs_x), ax, _stream()), "pmlp_gemm_pair")
+
+
+def _gemm_pair_dw0(jobs_w, ksplit, jobs_x, jobs_w0, ksplit0, fold=True, plan=False):
+    """_gemm_pair for the layer above the first, with the first layer's weight gradient jobs_w0
+    (no A: it is jobs_x's result) formed inside the input-gradient tiles where the shapes allow
+    (pmlp_gemm_pair_dw0: jobs_x then need no cb), else pmlp_gemm_pair and the PARTIAL_TN launch
+    on jobs_x's cb.  Returns whether it folded; plan=True only asks (no launch).  Bitwise the
+    slabs of the two launches either way."""
+    aw = (GemmJob * len(jobs_w))(*[_gemm_job(j) for j in jobs_w])
+    ax = (GemmJob * len(jobs_x))(*[_gemm_job(j) for j in jobs_x])
+    a0 = (GemmJob * len(jobs_w0))(*[_gemm_job(j) for j in jobs_w0])
+    if plan:
+        rc = load().pmlp_gemm_pair_dw0_plan(len(jobs_w), aw, ksplit, len(jobs_x), ax, len(jobs_w0), a0, ksplit0)
+        if rc < 0:
+            _ok(rc, "pmlp_gemm_pair_dw0_plan")
+        return bool(rc)
+    folded = C.c_int32(0)
+    _ok(load().pmlp_gemm_pair_dw0(len(jobs_w), aw, ksplit, len(jobs_x), ax, len(jobs_w0), a0, ksplit0, int(bool(fold)),
+                                  C.byref(folded), _stream()), "pmlp_gemm_pair_dw0")
+    return bool(folded.value)
 
 
 def _gemm(epi, jobs, ksplit=0):
