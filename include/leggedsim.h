@@ -122,7 +122,18 @@ typedef struct lgs_sim_params {
  * So planted feet cannot take the slots of a knee, hip or pelvis on the ground (its contact
  * force, the collision penalty and contact terminations depend on them).  Joint limits take
  * the limit rows in DOF order, then the rows of unused contact slots.  Whatever still does not
- * fit is counted: lgs_get_contact_stats. */
+ * fit is counted: lgs_get_contact_stats.
+ * The solve visits the rows in this order: the ground contacts (1. then 3.), the self contacts, the
+ * joint limits.  A ground contact's frame is n (the triangle's normal), t1 = normalise(e_x - n_x n),
+ * t2 = n x t1, its friction 0.5 * (ground_friction + shape friction).  A contact's normal row aims at
+ * -sep/dt over an open gap and at min(-baumgarte*sep/dt, max_depenetration_velocity) when it
+ * penetrates.  A joint-limit row is taken when the predicted position q + dt*qd_free leaves
+ * [lower, upper]; its target is -gap/dt, or -baumgarte*gap/dt when q is already beyond the limit
+ * (gap < 0), and max_depenetration_velocity does not clamp it: that parameter is PhysX's for
+ * contacts only.  Each sweep projects normal and limit impulses onto >= 0 and moves the two
+ * friction rows of a contact together, each by its own diagonal of J M^-1 J^T (+ 1e-9), then scales
+ * the pair back onto the disc of radius mu * lambda_n.  tests/phys_ref.py is these semantics in
+ * fp64 from the textbook definitions; tests/test_gpu_phys_reference.py holds the kernel to it. */
 
 /* ---- self-collision (IsaacGym create_actor collision filter, legged_robot.py:373-374:
  *      cfg.asset.self_collisions == 0 lets the links of one actor collide; see
@@ -130,7 +141,9 @@ typedef struct lgs_sim_params {
  *      body frame; the listed proxy pairs (never a body with itself or its parent) are
  *      tested every substep: closest points of the two segments, signed distance minus both
  *      radii and rest_offset, active below contact_offset.  A touching pair is one contact
- *      (normal from the second body to the first, a friction pair, the env's shape friction)
+ *      (normal from the second body to the first, acting at the midpoint of the two surfaces; a
+ *      friction pair t1 = normalise(e - (e.n) n), t2 = n x t1 with e = x, or e = y when |n_x| >=
+ *      0.57735 so that t1 stays well defined for a normal near the x axis; the env's shape friction)
  *      in the slots after the ground contacts; up to max_self_contacts of them per substep,
  *      first in pair order, after one slot per touching ground body (the slot order above).
  *      The contact force joins both bodies' net contact force with opposite signs.      */

@@ -56,11 +56,31 @@ def _momentum(spec, rbs):
     return (m[:, None] * v).sum(0)
 
 
-@pytest.mark.parametrize("task", ["go2", "h1"])
+def _angular_momentum(spec, rbs):
+    """About the system COM, from the rigid_body_states rows: sum m (c - c_sys) x v_c + R I R^T w."""
+    B = spec.num_bodies
+    md = spec.model
+    rows = rbs.reshape(-1, B, 13)[0].astype(np.float64)
+    m = md.mass.astype(np.float64)
+    L = np.zeros(3)
+    x, y, z, w = rows[:, 3], rows[:, 4], rows[:, 5], rows[:, 6]
+    R = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], -1),
+                  np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], -1),
+                  np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1)], -2)
+    c = rows[:, 0:3] + np.einsum("bij,bj->bi", R, md.com.astype(np.float64))
+    cs = (m[:, None] * c).sum(0) / m.sum()
+    for b in range(B):
+        i = md.inertia[b].astype(np.float64)
+        Ib = np.array([[i[0], i[3], i[4]], [i[3], i[1], i[5]], [i[4], i[5], i[2]]])
+        L += m[b] * np.cross(c[b] - cs, rows[b, 7:10]) + R[b] @ Ib @ R[b].T @ rows[b, 10:13]
+    return L
+
+
+@pytest.mark.parametrize("task", ["go2", "h1", "g1", "h1_2"])
 def test_zero_gravity_momentum_converges_first_order(task, oracle_lib):
-    """No external force: total linear momentum is constant up to the semi-implicit
-    Euler error, which must halve when dt halves (a wrong bias/Coriolis term would
-    leave an O(1) residual instead)."""
+    """No external force: total linear momentum, and the angular momentum about the system
+    COM, are constant up to the semi-implicit Euler error, which must halve when dt halves
+    (a wrong bias/Coriolis term would leave an O(1) residual instead)."""
     s = make_spec(task)
     rng = np.random.default_rng(0)
     qd0 = rng.normal(0, 3.0, s.num_dof).astype(np.float32)
@@ -75,14 +95,18 @@ def test_zero_gravity_momentum_converges_first_order(task, oracle_lib):
         dofs[:, 1] = qd0
         tau = np.zeros((1, s.num_dof), np.float32)
         _, rbs0 = sim(oracle_lib, s, root, dofs, tau, params, steps=1)
-        p0 = _momentum(s, rbs0)
+        p0, L0 = _momentum(s, rbs0), _angular_momentum(s, rbs0)
         _, rbs = sim(oracle_lib, s, root, dofs, tau, params, steps=int(round(T / dt)) - 1)
-        return np.abs(_momentum(s, rbs) - p0).max(), np.abs(p0).max()
+        return (np.abs(_momentum(s, rbs) - p0).max(), np.abs(p0).max(),
+                np.abs(_angular_momentum(s, rbs) - L0).max(), np.abs(L0).max())
 
-    d1, pmag = drift(0.004)
-    d2, _ = drift(0.002)
+    d1, pmag, a1, lmag = drift(0.004)
+    d2, _, a2, _ = drift(0.002)
+    print(f"{task}: linear drift {d1:.3e} -> {d2:.3e} of {pmag:.3e}; angular drift {a1:.3e} -> {a2:.3e} of {lmag:.3e}")
     assert d1 < 0.02 * max(pmag, 1.0)
     assert 0.35 < d2 / d1 < 0.65
+    assert a1 < 0.02 * max(lmag, 1.0)
+    assert 0.35 < a2 / a1 < 0.65
 
 
 def test_go2_stands_on_pd_and_feet_carry_weight(oracle_lib):
